@@ -3086,12 +3086,15 @@ extern "C" int cr_conv2d_bwd_weight_bias(cr_ctx* ctx, const void* dy, const void
 // `batches` float32 weight-gradient GEMMs of one shape in ONE launch: dw[b] (O,K) += dy[b] (R,O)^T x[b] (R,K) (f32 atomics over
 // the pixel splits), operands of batch b at base + b * stride elements -- the 16 products of a Winograd weight gradient
 // (csrc/winograd.hip).  One launch lets a block keep a long pixel range (12 splits instead of 170 per product: the atomics of a
-// 128 x 128 tile are paid 14 times less often).  dw must be zeroed (or hold what is to be added to).
+// 128 x 128 tile are paid 14 times less often).  dw must be zeroed (or hold what is to be added to).  Deterministic mode
+// (CR_DETERMINISTIC=1): split s stores its partial sums to slab[s][b * sdw + ...] (slab_stride spans all batches) and
+// k_wgrad_reduce adds the splits in a fixed order.
 __global__ __launch_bounds__(CONV_T) void k_wgrad_batched_f32(WgP p, long long sdy, long long sx, long long sdw, int count) {
     const long long b = blockIdx.y;
     p.dy = (const float*)p.dy + b * sdy;
     p.x = (const float*)p.x + b * sx;
     p.dw = p.dw + b * sdw;
+    if (p.slab) p.slab = p.slab + b * sdw;
     conv_wgrad_f32_body<128, 1>(p, (int)blockIdx.x, count);
 }
 
@@ -3117,8 +3120,16 @@ extern "C" int cr_wgrad_batched_f32(cr_ctx* ctx, const float* dy, const float* x
     splits = (nsteps + p.steps_per_split - 1) / p.steps_per_split;
     p.tm = tm; p.tn = tn; p.xcd = xcd_enabled();
     const int count = tm * tn * splits;
+    const int64_t n = (int64_t)batches * stride_dw;
+    if (deterministic_on() && ctx->ws && stride_dw == (int64_t)O * K && (size_t)splits * n * sizeof(float) <= ctx->ws_bytes) {
+        p.slab = (float*)ctx->ws;
+        p.slab_stride = (long)n;
+    }
     hipLaunchKernelGGL(k_wgrad_batched_f32, dim3((unsigned)count, (unsigned)batches), dim3(CONV_T), 0, ctx->stream, p,
                        (long long)stride_dy, (long long)stride_x, (long long)stride_dw, count);
+    if (p.slab)
+        hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)cr_cdiv(n, 256)), dim3(256), 0, ctx->stream, p.slab, splits, p.slab_stride,
+                           (long)n, dw);
     CR_LAUNCH_CHECK();
     return CR_OK;
 }

@@ -871,9 +871,14 @@ def wino_conv3x3_group(srcs, w_krsc, dsts, bias, relu, accs, backward, keep_v=Fa
 
 
 def wino_wgrad_on():
-    """the Winograd weight gradient (CR_WINO_WGRAD, default on) accumulates over pixel splits with f32 atomics: the
-    bit-reproducible mode (CR_DETERMINISTIC=1) keeps the direct kernels with their fixed-order reduce"""
-    return os.environ.get("CR_WINO_WGRAD", "1") != "0" and os.environ.get("CR_DETERMINISTIC", "0") in ("", "0")
+    """the Winograd weight gradient (CR_WINO_WGRAD, default on); in the bit-reproducible mode (CR_DETERMINISTIC=1) its pixel
+    splits are added in a fixed order (cr_wgrad_batched_f32) and the bias gradient is a fixed-order column sum"""
+    return os.environ.get("CR_WINO_WGRAD", "1") != "0"
+
+
+def deterministic_on():
+    """CR_DETERMINISTIC=1: every weight-gradient reduce in a fixed order (read by the library at its first weight gradient)"""
+    return os.environ.get("CR_DETERMINISTIC", "0") not in ("", "0")
 
 
 def wino_wgrad_group(gs, xs, w_sink, b_sink, v_saved=None):
@@ -895,10 +900,16 @@ def wino_wgrad_group(gs, xs, w_sink, b_sink, v_saved=None):
     else:
         _chk(lib.cr_wino_input(ctx, len(xs), cast(_ptr_table(xs)), cast(Ns), cast(Hs), cast(Ws), C, _p(V), T), "cr_wino_input")
     U.zero_()
-    part = U[16 * O * C:] if b_sink is not None else None
+    # the bias gradient rides on the dY transform (atomics over partial rows), or, deterministic, is a fixed-order column sum
+    part = U[16 * O * C:] if b_sink is not None and not deterministic_on() else None
+    if b_sink is not None and part is None:
+        ws = torch.empty((1024, O), dtype=torch.float32, device=dev)
+        for g in gs:
+            _chk(lib.cr_colsum_accum(ctx, _p(g), 1, g.numel() // O, O, _p(ws), _p(b_sink)), "cr_colsum_accum")
     _chk(lib.cr_wino_dy(ctx, len(gs), cast(_ptr_table(gs)), cast(Ns), cast(Hs), cast(Ws), O, _p(M), T, _p(part)), "cr_wino_dy")
     _chk(lib.cr_wgrad_batched_f32(ctx, _p(M), _p(V), _p(U), T, C, O, 16, T * O, T * C, O * C), "cr_wgrad_batched_f32")
-    _chk(lib.cr_wino_filter_grad(ctx, _p(U), _p(w_sink), O, C, _p(part), _p(b_sink)), "cr_wino_filter_grad")
+    _chk(lib.cr_wino_filter_grad(ctx, _p(U), _p(w_sink), O, C, _p(part), _p(b_sink) if part is not None else None),
+         "cr_wino_filter_grad")
 
 
 class _ConvBiasGroup(torch.autograd.Function):

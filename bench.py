@@ -1,11 +1,18 @@
 #!/usr/bin/env python
 """bench.py -- measures the hot path on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train|geometry|inference|weak|depth]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train|geometry|inference|weak|depth|boxnet]
+                    [--dump-outputs DIR] [--full]
 
 N>1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 (one rank per GPU, RCCL).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--full adds everything else the line has carried: CPU baselines, per-kernel roofline figures that take runs of their own,
+the other precision modes, the eager and do_train variants of the train step, the secondary workloads inside the train
+line, the data-parallel all-reduce measurement and parameter-sync check.
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (rank 0; see dump_outputs).
 
 Workloads
   geometry  BASELINE.json configs[2]: ProposalNetwork 1000-cube/object project + IoU/size/corner
@@ -63,6 +70,54 @@ def max_over_ranks(x, world, dev):
     t = torch.tensor([x], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
+
+
+DUMP_MAX_ELEMS = 1 << 20        # per array: a larger output is written as a fixed, seeded sample of this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def output_tensors(obj, name=""):
+    """name -> tensor for every tensor in a step's result: dicts by key, Instances by field, Boxes by their tensor; a list
+    (one entry per image) is concatenated per name after flattening each entry"""
+    join = lambda k: f"{name}.{k}" if name else str(k)
+    if torch.is_tensor(obj):
+        return {name or "out": obj}
+    if hasattr(obj, "get_fields"):
+        obj = obj.get_fields()
+    elif torch.is_tensor(getattr(obj, "tensor", None)):
+        return {name or "out": obj.tensor}
+    out = {}
+    if isinstance(obj, dict):
+        for k, v in obj.items():
+            out.update(output_tensors(v, join(k)))
+    elif isinstance(obj, (list, tuple)):
+        parts = [output_tensors(v, name) for v in obj]
+        for k in dict.fromkeys(k for p in parts for k in p):
+            out[k] = torch.cat([p[k].detach().reshape(-1) for p in parts if k in p])
+    return out
+
+
+def dump_outputs(args, outputs):
+    """--dump-outputs DIR: `outputs` (name -> tensor, see output_tensors) as DIR/<name>.npy ("/" in a name becomes ".").
+    Floating-point arrays are written in float32 (float64 stays float64), integer and boolean ones in float64 (exact).  An
+    array of more than DUMP_MAX_ELEMS elements is written flattened, as its elements at DUMP_MAX_ELEMS flat indices drawn
+    with a fixed seed (the same indices in every run of the same shape), so two builds of the project can be compared output
+    for output.  Nothing is written when the total would exceed DUMP_MAX_BYTES."""
+    arrays = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        t = t.cpu()
+        arrays[name.replace("/", ".")] = (t.double() if not t.is_floating_point() else t if t.dtype == torch.float64
+                                          else t.float()).numpy()                      # "BoxHead/loss_box_reg"
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total / 2**20:.1f} MB of outputs, more than {DUMP_MAX_BYTES >> 20} MB")
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------
@@ -159,6 +214,8 @@ def bench_geometry(args, rank, world, dev, argmax_only=False, inp=None, cpu_base
     dt = time.perf_counter() - t0
     dt = max_over_ranks(dt, world, dev)
     kern_ms = ev0.elapsed_time(ev1) / args.steps       # events on the stream the kernel is launched on
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args, output_tensors(bufs))
     cubes_total = n_obj * P * world
     value = cubes_total * args.steps / dt
     bytes_per_cube = 60 if argmax_only else 60 + 64 + 16 + 16    # read 60 B (+ corners 64 + box 16 + 4 score planes)
@@ -180,7 +237,7 @@ def bench_geometry(args, rank, world, dev, argmax_only=False, inp=None, cpu_base
                      "traffic": pmc_traffic(GEOMETRY_PMC[(exact, argmax_only)], "k_project_score"),
                      "algorithmic_bytes_per_launch": bytes_per_cube * n_obj * P, "kernel_ms": kern_ms},
     }
-    if rank == 0 and world == 1 and cpu_baseline and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and cpu_baseline and getattr(args, "full", False) and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline_geometry(inp, P)
     return res
 
@@ -219,7 +276,7 @@ def bench_inference(args, rank, world, dev):
     if os.environ.get("CR_GRAPHS", "dense") != "none":
         with torch.no_grad(), d2.EventStorage(0):
             model.enable_graphs_eval(batches[0])         # forward-only HIP graph of preprocess + trunk + FPN + RPN head
-    n_det = 0
+    n_det, out = 0, None
     with torch.no_grad(), d2.EventStorage(0):
         for i in range(args.warmup):
             model(batches[i % 2])
@@ -230,13 +287,15 @@ def bench_inference(args, rank, world, dev):
             n_det += sum(len(o["instances"]) for o in out)
         barrier(world)
         dt = max_over_ranks(time.perf_counter() - t0, world, dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args, output_tensors(out))
     prec = importlib.import_module("3dod_amd.hipops").precision()
     gflop_img = 116.8                    # 58.4 GMAC per 512x512 image with 1000 RoIs
     ach = gflop_img * B / (dt / args.steps) / 1e3
     res = _inference_result(args, world, B, dt, n_det, prec, ach, bt.MFMA_PEAK[prec], gflop_img)
     del model, opt
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and getattr(args, "full", False) and not args.no_cpu_baseline:
         res["cpu_baseline"] = bt.cpu_baseline_train(inference=True, steps=getattr(args, "cpu_steps", None))
     return res
 
@@ -283,15 +342,20 @@ def bench_boxnet(args, rank, world, dev):
     nobj = sum(len(b["instances"]) for b in batch)
     gen = torch.Generator(device=dev).manual_seed(3 + rank)
     run = lambda: model.inference(batch, experiment_type={"use_pred_boxes": False}, generator=gen)
+    out = None
     with torch.no_grad():
         for _ in range(args.warmup):
             run()
         barrier(world)
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            run()
+            out = run()
         barrier(world)
         dt = max_over_ranks(time.perf_counter() - t0, world, dev)
+    if rank == 0 and getattr(args, "dump_outputs", None):
+        dump_outputs(args, output_tensors(out))
+    if not getattr(args, "full", False):
+        return boxnet_line(args, world, dt, B, nobj, {})
     # roofline of the pipeline's dominant stage (rocprofv3: k_ccl_merge / k_mask_rect / k_ccl_sizes lead the kernel time):
     # the six kernels of cr_mask_rects on this batch's masks, HIP events on the launch stream.  Algorithmic bytes (DESIGN
     # section 2): the mask once (1 B / pixel of every 512 x 512 mask: the bounding-window search reads all of it) + one
@@ -321,6 +385,10 @@ def bench_boxnet(args, rank, world, dev):
     extra = {"roofline": roofline}
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         extra["cpu_baseline"] = cpu_baseline_boxnet(batch[0], n_obj, seconds=getattr(args, "cpu_seconds", 12.0))
+    return boxnet_line(args, world, dt, B, nobj, extra)
+
+
+def boxnet_line(args, world, dt, B, nobj, extra):
     return {**extra,
             "metric": "images/sec BoxNet 1000-cube proposal-and-scoring pipeline on GT boxes (BASELINE configs[2], end to end)",
             "value": B * world * args.steps / dt, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -425,7 +493,9 @@ def bench_weak(args, rank, world, dev):
         dt = max_over_ranks(time.perf_counter() - t0, world, dev)
         rep = step.report()
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args, importlib.import_module("bench_train").step_outputs(step, opt))
+    if rank == 0 and getattr(args, "full", False):
         # the dominant launches of this step are the same grouped pyramid convolutions as in the supervised step, at 2 images
         extra["roofline"] = bt.dominant_kernel_roofline(dev, importlib.import_module("3dod_amd.hipops").precision(), images=B)
         if world == 1 and not args.no_cpu_baseline:
@@ -505,11 +575,13 @@ def bench_depth(args, rank, world, dev):
             d = run(xs[i % 2])
         barrier(world)
     dt = max_over_ranks(time.perf_counter() - t0, world, dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args, {"depth": d})
     assert bool(torch.isfinite(d).all())
     gflop = depth_model_gflop(B, 24, 1024, [256, 512, 1024, 1024], 256, S // 14, S // 14)
     ach = gflop * B / (dt / args.steps) / 1e3
     extra = {}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and getattr(args, "full", False) and not args.no_cpu_baseline:
         extra["cpu_baseline"] = cpu_baseline_depth(model, S)
     return {**extra, "metric": "images/sec Depth-Anything-V2 ViT-L forward (depth backbone of BASELINE configs[4])",
             "value": B * world * args.steps / dt, "unit": "images/s", "n_gpus": world, "steps": args.steps,
@@ -547,12 +619,24 @@ def main():
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--workload", default="train", choices=["train", "geometry", "inference", "weak", "depth", "boxnet"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, roofline / per-kernel figures, other precisions, secondary workloads and checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, <= 64 MB); "
+                         "weight-gradient pixel splits are added in a fixed order instead of with atomics (same kernels)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without the CPU baselines")
     ap.add_argument("--argmax-only", action="store_true", help="geometry workload: the AP path (no output planes)")
     ap.add_argument("--exact-planes", action="store_true", help="geometry workload: cr_cubes_project_score (bit-exact planes)")
-    ap.add_argument("--train-only", action="store_true", help="train workload without the geometry / inference keys")
-    ap.add_argument("--lean", action="store_true", help="headline measurement only (no eager / do_train / other-precision lines)")
+    ap.add_argument("--train-only", action="store_true", help="with --full: train workload without the geometry / inference keys")
+    ap.add_argument("--lean", action="store_true", help="with --full: no eager / do_train / other-precision lines")
     args = ap.parse_args()
+    if args.dump_outputs:
+        # by default the train / weak steps add the pixel splits of every weight gradient with f32 atomics: last-bit
+        # differences from run to run that the following steps amplify (RoI sampling, NMS) far beyond rounding.  A run whose
+        # outputs are compared runs the same kernels and routes (the Winograd weight gradient included), but each split stores
+        # its partial sums and a second pass adds them in a fixed order (CR_DETERMINISTIC=1, read by the library at its first
+        # weight gradient): the same arguments give the same bits.  The result line reports it (weight_gradient_reduce).
+        os.environ["CR_DETERMINISTIC"] = "1"
     if args.steps is None:
         args.steps = 200 if args.workload == "geometry" else 20
     if args.warmup is None:
@@ -573,14 +657,14 @@ def main():
     else:
         bt = importlib.import_module("bench_train")
         res = bt.bench_train(args, rank, world, dev)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if rank == 0 and world == 1 and getattr(args, "full", False) and not args.no_cpu_baseline:
             res["cpu_baseline"] = bt.cpu_baseline_train(steps=2)
-        if world == 1 and not args.train_only:
+        if world == 1 and getattr(args, "full", False) and not args.train_only:
             # the other two workloads north_star names, in the SAME line (labelled keys; each with its own roofline and
             # cpu_baseline): the 1000-cube geometry (BASELINE configs[2]; full outputs, the argmax-only AP path, the whole
             # BoxNet proposal-and-scoring pipeline around it) and detector inference at 8 x 512 x 512 (configs[1]).
             # `value` above stays the train step.
-            sub = argparse.Namespace(**vars(args))
+            sub = argparse.Namespace(**dict(vars(args), dump_outputs=None))      # the dump is the headline step's
             keep = ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "dtype", "config", "roofline", "cpu_baseline")
             for key, fn, st, wu, kw in (("geometry", bench_geometry, 200, 20, {}),
                                         ("geometry_argmax_only", bench_geometry, 200, 20, {"argmax_only": True, "cpu_baseline": False}),

@@ -2,9 +2,10 @@
 forward + losses + backward + gradient all-reduce + SGD-momentum update, every step.
 
 The headline line is measured in the REFERENCE'S precision: float32 activations / operands on the f32 MFMA
-(the reference trains without autocast, tools/train_net.py:184-330), roofline against the 157.3 TFLOP/s f32 peak.
-At N = 1 the same step is then re-measured in the bf16 fast mode and reported inside the same JSON line under
-"bf16_mode" (labelled; it is NOT the headline: tests/test_gpu_precision_parity.py bounds its deviation)."""
+(the reference trains without autocast, tools/train_net.py:184-330).  With `bench.py --full` the line also carries the
+roofline against the 157.3 TFLOP/s f32 peak, and at N = 1 the same step is re-measured in the fp32x3 and bf16 modes and
+reported inside the same JSON line under "fp32x3_mode" / "bf16_mode" (labelled; NOT the headline:
+tests/test_gpu_precision_parity.py bounds the bf16 deviation)."""
 import importlib
 import json
 import os
@@ -52,6 +53,8 @@ def bench_train(args, rank, world, dev):
     ops = importlib.import_module("3dod_amd.hipops")
     main_prec = ops.precision()                          # fp32 unless CR_PRECISION=bf16 was asked for explicitly
     res = _bench_train_mode(args, rank, world, dev, main_prec)
+    if not getattr(args, "full", False):
+        return res
     notes = {"fp32x3": "same step, float32 storage, contractions through the exact three-way bf16 operand split (float32 "
                        "accuracy, opt-in: CR_PRECISION=fp32x3); not the headline",
              "bf16": "same step with bf16 activations / operands (fast mode, opt-in); not the headline; deviation from "
@@ -130,10 +133,16 @@ def _bench_train_mode(args, rank, world, dev, prec, is_main=True):
         note("timed loop done")
         dt = B.max_over_ranks(time.perf_counter() - t0, world, dev)
         rep = step.report()
+    if is_main and rank == 0 and getattr(args, "dump_outputs", None):
+        B.dump_outputs(args, step_outputs(step, opt))
     ims = IMS_PER_GPU * world * args.steps / dt
     achieved_tf = TRAIN_GFLOP_PER_IMAGE * IMS_PER_GPU / (dt / args.steps) / 1e3
     comm = {"world_size": world, "backend": "none (single process)"}
-    if world > 1:
+    full = getattr(args, "full", False)
+    if world > 1 and not full:
+        import torch.distributed as dist
+        comm = {"world_size": world, "backend": dist.get_backend()}
+    if world > 1 and full:
         # the step's one real exchange on its own: all-reduce of the flat float32 gradient over RCCL, so that a scaling
         # run explains itself (bus bandwidth = 2 (n-1)/n x bytes / time, the ring's per-link figure)
         import torch.distributed as dist
@@ -165,7 +174,7 @@ def _bench_train_mode(args, rank, world, dev, prec, is_main=True):
             raise RuntimeError("data-parallel ranks hold different parameters after the run")
         del buf
     eager = None
-    if world == 1 and mode != "none" and is_main and os.environ.get("CR_BENCH_EAGER", "1") == "1" \
+    if world == 1 and mode != "none" and is_main and full and os.environ.get("CR_BENCH_EAGER", "1") == "1" \
             and not getattr(args, "lean", False):
         # the same step with every kernel launched eagerly (CR_GRAPHS=none): what the dense-region graphs buy
         saved = (model._graphed, model._graphed_cache, model._graphed_max)
@@ -185,6 +194,55 @@ def _bench_train_mode(args, rank, world, dev, prec, is_main=True):
                      "launch_mode": "eager (CR_GRAPHS=none): every kernel of the dense region enqueued by the host"}
         finally:
             model._graphed, model._graphed_cache, model._graphed_max = saved
+    kern = roofline(model, step, batches, dev, prec, peak) if full else None
+    note("roofline done")
+    import sys
+    print(f"[bench] rank {rank} [{prec}]: {ims:.1f} images/s, {dt / args.steps * 1e3:.2f} ms/step", file=sys.stderr, flush=True)
+    res = {
+        "metric": "images/sec Cube R-CNN DLA34-FPN train step", "value": ims, "unit": "images/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": prec, "data": "synthetic",
+        "config": {"workload": "Cube R-CNN DLA34+FPN train step (fwd+loss+bwd+allreduce+SGD), 4 img/GPU 512x512, "
+                               "Base_Omni3D.yaml semantics (BASELINE configs[3] per-GPU shard)",
+                   "global_batch": IMS_PER_GPU * world, "parallelism": f"dp{world}", "base_lr": cfg.SOLVER.BASE_LR,
+                   "precision": PRECISION_TEXT[prec],
+                   "weight_gradient_reduce": "pixel splits stored and added in a fixed order (CR_DETERMINISTIC=1)"
+                                             if importlib.import_module("3dod_amd.hipops").deterministic_on() else "f32 atomics",
+                   "launch_mode": {"step": "whole-step HIP graphs (solver.GraphedTrainStep, opt-in)",
+                                   "dense": "solver.make_train_step = the step object of do_train / tools/train_net.py: dense region "
+                                            "(preprocess, trunk, FPN, RPN head; forward and backward) replayed from per-shape HIP graphs",
+                                   "none": "eager"}[mode],
+                   "final_loss": rep.get("total_loss"), "skipped_steps": rep.get("iterations_explode"),
+                   "valid": bool(rep.get("iterations_explode") == 0 and rep.get("total_loss") == rep.get("total_loss")),
+                   "comm": comm},
+    }
+    if kern is not None:
+        res["roofline"] = dict(kern, whole_step={"achieved": achieved_tf, "unit": "TFLOP/s",
+                                                 "frac": achieved_tf / peak,
+                                                 "algorithmic_gflop_per_step": TRAIN_GFLOP_PER_IMAGE * IMS_PER_GPU,
+                                                 "note": "direct-form flops of the step / wall time: an effective rate -- in float32 the "
+                                                         "pyramid heads' 3x3 layers execute 2.25x fewer multiplies (Winograd); the "
+                                                         "per-kernel figures above count the flops the kernel executes"})
+    if eager is not None:
+        res["eager"] = eager
+    del step, model, opt
+    torch.cuda.empty_cache()
+    return res
+
+
+def step_outputs(step, opt):
+    """what a caller of the train step receives from its last call: the loss terms by name, the (all-reduced) total, the skip
+    flag -- and what the step leaves behind: the flat parameters and gradient (bench.dump_outputs writes a seeded sample)"""
+    last = step.last
+    out = dict(zip(last["keys"], last["values"]))
+    out.update(total_loss=last["total"], skipped=last["skipped"], params=opt.flat_p, grads=opt.flat_g)
+    return out
+
+
+def roofline(model, step, batches, dev, prec, peak):
+    """bench.py --full: the dominant kernel's roofline, in-step (dominant_kernel_in_step) beside the micro-benchmark
+    (dominant_kernel_roofline)"""
+    d2 = importlib.import_module("3dod_amd.d2lite")
     ins, ins_err = None, None
     try:                             # (before the micro-benchmark: the profile's last three optimizer updates are these steps)
         with d2.EventStorage(0):
@@ -212,36 +270,7 @@ def _bench_train_mode(args, rank, world, dev, prec, is_main=True):
             kern["traffic"] = pmc_traffic_for(kern["kernel"], prec, IMS_PER_GPU)
     except Exception as e:           # never lose the headline to the instrumentation
         kern["in_step_error"] = f"{type(e).__name__}: {e}"
-    note("roofline done")
-    import sys
-    print(f"[bench] rank {rank} [{prec}]: {ims:.1f} images/s, {dt / args.steps * 1e3:.2f} ms/step", file=sys.stderr, flush=True)
-    res = {
-        "metric": "images/sec Cube R-CNN DLA34-FPN train step", "value": ims, "unit": "images/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": prec, "data": "synthetic",
-        "config": {"workload": "Cube R-CNN DLA34+FPN train step (fwd+loss+bwd+allreduce+SGD), 4 img/GPU 512x512, "
-                               "Base_Omni3D.yaml semantics (BASELINE configs[3] per-GPU shard)",
-                   "global_batch": IMS_PER_GPU * world, "parallelism": f"dp{world}", "base_lr": cfg.SOLVER.BASE_LR,
-                   "precision": PRECISION_TEXT[prec],
-                   "launch_mode": {"step": "whole-step HIP graphs (solver.GraphedTrainStep, opt-in)",
-                                   "dense": "solver.make_train_step = the step object of do_train / tools/train_net.py: dense region "
-                                            "(preprocess, trunk, FPN, RPN head; forward and backward) replayed from per-shape HIP graphs",
-                                   "none": "eager"}[mode],
-                   "final_loss": rep.get("total_loss"), "skipped_steps": rep.get("iterations_explode"),
-                   "valid": bool(rep.get("iterations_explode") == 0 and rep.get("total_loss") == rep.get("total_loss")),
-                   "comm": comm},
-        "roofline": dict(kern, whole_step={"achieved": achieved_tf, "unit": "TFLOP/s",
-                                           "frac": achieved_tf / peak,
-                                           "algorithmic_gflop_per_step": TRAIN_GFLOP_PER_IMAGE * IMS_PER_GPU,
-                                           "note": "direct-form flops of the step / wall time: an effective rate -- in float32 the "
-                                                   "pyramid heads' 3x3 layers execute 2.25x fewer multiplies (Winograd); the "
-                                                   "per-kernel figures above count the flops the kernel executes"}),
-    }
-    if eager is not None:
-        res["eager"] = eager
-    del step, model, opt
-    torch.cuda.empty_cache()
-    return res
+    return kern
 
 
 def bench_do_train(args, rank, world, dev):

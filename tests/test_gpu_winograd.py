@@ -99,7 +99,7 @@ def test_weight_gradient_against_float64(sizes, C, O):
 
 def test_autograd_weight_gradient_into_sinks(monkeypatch):
     """parameters with gradient sinks (what FlatSGD attaches): the op's weight / bias gradients land in the sinks, Winograd route
-    and direct route (CR_WINO_WGRAD=0) agreeing to float32 rounding; CR_DETERMINISTIC=1 keeps the direct kernels"""
+    and direct route (CR_WINO_WGRAD=0) agreeing to float32 rounding; CR_DETERMINISTIC=1 keeps the Winograd route"""
     if ops.precision() != "fp32":
         pytest.skip("float32 route")
     monkeypatch.setattr(ops, "WINO_MIN_TILES", 1024)
@@ -135,4 +135,4 @@ def test_autograd_weight_gradient_into_sinks(monkeypatch):
     # atomics order differs run to run: float32 rounding only
     assert float((w._cr_grad - res[("1", True)][0]).abs().max()) <= 2e-5 * float(w._cr_grad.abs().max())
     monkeypatch.setenv("CR_DETERMINISTIC", "1")
-    assert not ops.wino_wgrad_on()
+    assert ops.wino_wgrad_on() and ops.deterministic_on()     # fixed-order split sums, same route

@@ -36,7 +36,6 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define CONV_T 256
-#define STAT_REPL 32        // (legacy name) -- BN statistics are now per-block partial sums, reduced in a fixed order
 
 struct ConvP {
     const void* x;       // gather source, NHWC bf16 or f32 (fwd: input; bwd-data: dY)
@@ -48,7 +47,6 @@ struct ConvP {
     int N, Hin, Win, Cin, Hout, Wout, Cout;
     int stride, pad, Kdim, M, cshift, relu;
     unsigned x_bytes, w_bytes;   // extents for the buffer-load descriptors (out-of-range voffset reads 0)
-    int xcd;                     // 1 = XCD-aware tile order
     int f32;                     // 1 = f32 operands / outputs (host-side dispatch only)
     // split-K over workgroups (k_conv_igemm_dma): ksplit > 1 -> block (tile, s) accumulates k stages [s*kstages, ...) and
     // stores its raw f32 accumulators to part[s][M][Cout]; k_splitk_epilogue sums them in a fixed order and applies the
@@ -273,7 +271,7 @@ __global__ __launch_bounds__(CONV_T * KG) void k_conv_igemm(ConvP p) {
     u16* sX = sXall + grp * XE;
     u16* sW = sWall + grp * WE;
     const int n_tiles = p.Cout / BN;
-    int bid = p.xcd ? xcd_swizzle(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    int bid = xcd_swizzle(blockIdx.x, gridDim.x);
     // parity-class mode (stride-2 backward-data): the grid is 4 classes x tiles; this block's class, its taps and k extent
     int ph = 0, pw = 0, nsr = KS, kdim = p.Kdim;
     unsigned tapr = 0, taps_ = 0;                 // packed lists (2 bits each) of the filter rows / columns of the class
@@ -534,7 +532,7 @@ __device__ __forceinline__ void conv_igemm_dma_body(const ConvP& p, const int bl
     const int n_tiles = p.Cout / BN;
     const int tiles_total = blk_count / p.ksplit;                           // ksplit == 1: the whole grid
     const int ks = blk_id / tiles_total, bt = blk_id - ks * tiles_total;
-    const int bid = (p.xcd && (p.ksplit == 1 || (tiles_total & 7) == 0)) ? xcd_swizzle(bt, tiles_total) : bt;
+    const int bid = (p.ksplit == 1 || (tiles_total & 7) == 0) ? xcd_swizzle(bt, tiles_total) : bt;
     const int nt = bid % n_tiles, mt = bid / n_tiles;
     const int m0 = mt * BM, n0 = nt * BN;
 
@@ -744,7 +742,7 @@ __global__ __launch_bounds__(CONV_T) void k_conv_igemm_dma_s3(ConvP p) {
     const int n_tiles = p.Cout / BN;
     const int tiles_total = (int)gridDim.x / p.ksplit;
     const int ks = (int)blockIdx.x / tiles_total, bt = (int)blockIdx.x - ks * tiles_total;
-    const int bid = (p.xcd && (p.ksplit == 1 || (tiles_total & 7) == 0)) ? xcd_swizzle(bt, tiles_total) : bt;
+    const int bid = (p.ksplit == 1 || (tiles_total & 7) == 0) ? xcd_swizzle(bt, tiles_total) : bt;
     const int nt = bid % n_tiles, mt = bid / n_tiles;
     const int m0 = mt * BM, n0 = nt * BN;
 
@@ -1041,14 +1039,8 @@ static int launch_igemm_f32(cr_ctx* ctx, const ConvP& p) {
     return CR_OK;
 }
 
-static int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-static int xcd_enabled() {
-    static const int v = env_int("CR_XCD", 1);
-    return v;
-}
+// what a try_launch_* route returns when the layer does not take it (every other value is the launch status)
+static constexpr int NOT_TAKEN = 1;
 
 // literal template arguments from a plain function (the launch from inside a function template left the host stubs undefined)
 static void launch_dma_kernel(int bn, int ks, int mode, hipStream_t stream, const ConvP& p, int bm = 128) {
@@ -1067,8 +1059,7 @@ static void launch_dma_kernel(int bn, int ks, int mode, hipStream_t stream, cons
 #undef CR_S3_CASE
     }
     // f32, at most one block per CU: two wave groups per block (see the kernel)
-    static const int kg_on = env_int("CR_CONV_KG2", 1);
-    const bool kg2 = kg_on && p.f32 && grid.x <= 256 && (p.Kdim / (p.f32 ? 32 : 64)) / p.ksplit >= 4;
+    const bool kg2 = p.f32 && grid.x <= 256 && (p.Kdim / (p.f32 ? 32 : 64)) / p.ksplit >= 4;
 #define CR_DMA_CASE(B, K, M_) if (bn == B && ks == K && mode == M_) { \
         if (kg2) hipLaunchKernelGGL((k_conv_igemm_dma<B, K, M_, float, 2>), grid, dim3(CONV_T * 2), 0, stream, p); \
         else if (p.f32) hipLaunchKernelGGL((k_conv_igemm_dma<B, K, M_, float>), grid, block, 0, stream, p); \
@@ -1079,23 +1070,21 @@ static void launch_dma_kernel(int bn, int ks, int mode, hipStream_t stream, cons
 #undef CR_DMA_CASE
 }
 
-static int dma_enabled() {
-    static const int v = env_int("CR_CONV_DMA", 1);
-    return v;
-}
+// split-K target: blocks in flight over the k split (one per CU; twice that for the very long k of the box head's FC)
+static constexpr int DMA_SPLITK_TARGET = 256;
+// below this many 128 x 128 output tiles, bf16 / no-split layers keep the 64x64 / split-K kernels
+static constexpr int DMA_MIN_TILES = 128;
 
-// true + launched if the layer takes the LDS-DMA kernel: the layers that would run <128,128> or <128,64> tiles with KU = 1
+// launched if the layer takes the LDS-DMA kernel: the layers that would run <128,128> or <128,64> tiles with KU = 1
 template <int KS, int MODE>
-static bool try_launch_dma(cr_ctx* ctx, const ConvP& p, int out_f32, int* rc) {
+static int try_launch_dma(cr_ctx* ctx, const ConvP& p, int out_f32) {
     if constexpr (KS == 7) {
-        return false;
+        return NOT_TAKEN;
     } else {
         // a k stage is two 64-B rows: 64 bf16 / 32 f32 of k, and must not straddle a filter tap
-        if (p.cls || (!p.f32 && out_f32) || !dma_enabled() || (p.Cin & (p.f32 ? 31 : 63)) != 0 || p.Cout % 64 != 0) return false;
-        static const int min_tiles = env_int("CR_CONV_DMA_MIN_TILES", 128), force_bn = env_int("CR_CONV_DMA_BN", 0);
+        if (p.cls || (!p.f32 && out_f32) || (p.Cin & (p.f32 ? 31 : 63)) != 0 || p.Cout % 64 != 0) return NOT_TAKEN;
         const int64_t big_tiles = cr_cdiv(p.M, 128) * (p.Cout >= 128 ? p.Cout / 128 : 1);
-        static const int splitk_on = env_int("CR_CONV_SPLITK", 1);
-        if (p.f32 && splitk_on && big_tiles < 192 && ctx->ws && (p.Kdim >= 2048 || (KS == 3 && p.Kdim >= 1152))) {
+        if (p.f32 && big_tiles < 192 && ctx->ws && (p.Kdim >= 2048 || (KS == 3 && p.Kdim >= 1152))) {
             // f32 mode, few big tiles: the small-tile kernels are L2-bandwidth bound there (a 64 x 32 tile moves 0.094 B
             // per flop = 14.7 TB/s at the f32 MFMA peak, a 128 x 128 tile 0.031), so keep 128-wide tiles and split K over
             // workgroups until every CU has one; partial sums go to the ctx workspace, k_splitk_epilogue finishes
@@ -1103,24 +1092,20 @@ static bool try_launch_dma(cr_ctx* ctx, const ConvP& p, int out_f32, int* rc) {
             int64_t tiles = cr_cdiv(p.M, 128) * (p.Cout / bn2);
             const int nstage_all = p.Kdim / 32;
             // half-height tiles first: twice the blocks before any k split (no slab traffic, often no epilogue launch)
-            static const int bm64_on = env_int("CR_CONV_BM64", 1);
             // very long k with >= 128 big tiles (the box head's first FC layer: 2048 x 12544 -> 1024): 128 x 128 tiles, split k
             // until there are two blocks per CU (scripts/fc_bench.py: 509 -> 450 us; the slabs are 1 % of the operand reads)
             const bool long_k = KS == 1 && p.Kdim >= 8192 && tiles >= 128;
-            const int bm = (bm64_on && !p.w3 && bn2 == 128 && p.M >= 128 && !long_k) ? 64 : 128;
+            const int bm = (!p.w3 && bn2 == 128 && p.M >= 128 && !long_k) ? 64 : 128;
             if (bm == 64) tiles = cr_cdiv(p.M, 64) * (p.Cout / 128);
-            static const int sk_target = env_int("CR_SPLITK_TARGET", 256);
-            int S = (int)cr_cdiv(long_k ? 2 * sk_target : sk_target, tiles);
+            int S = (int)cr_cdiv(long_k ? 2 * DMA_SPLITK_TARGET : DMA_SPLITK_TARGET, tiles);
             if (S > nstage_all / 4) S = nstage_all / 4;                      // >= 4 stages (128 of k) per block
             if (S > 16) S = 16;
             const int64_t cap = (int64_t)(ctx->ws_bytes / ((size_t)p.M * p.Cout * sizeof(float)));
             if (S > cap) S = (int)cap;
             if (S < 2 && bm == 64) {
                 launch_dma_kernel(128, KS, MODE, ctx->stream, p, 64);
-                hipError_t e3 = hipGetLastError();
-                if (e3 != hipSuccess) { cr_set_error("k_conv_igemm_dma launch failed: %s", hipGetErrorString(e3)); *rc = CR_EHIP; }
-                else *rc = CR_OK;
-                return true;
+                CR_LAUNCH_CHECK();
+                return CR_OK;
             }
             if (S >= 2) {
                 ConvP q = p;
@@ -1130,21 +1115,17 @@ static bool try_launch_dma(cr_ctx* ctx, const ConvP& p, int out_f32, int* rc) {
                 launch_dma_kernel(bn2, KS, MODE, ctx->stream, q, bm);
                 const dim3 g2((unsigned)cr_cdiv(p.M, 64), (unsigned)(p.Cout / 64));
                 hipLaunchKernelGGL(k_splitk_epilogue<float>, g2, dim3(256), 0, ctx->stream, q);
-                hipError_t e2 = hipGetLastError();
-                if (e2 != hipSuccess) { cr_set_error("split-K conv launch failed: %s", hipGetErrorString(e2)); *rc = CR_EHIP; }
-                else *rc = CR_OK;
-                return true;
+                CR_LAUNCH_CHECK();
+                return CR_OK;
             }
         }
-        if (big_tiles < min_tiles) return false;             // small grids keep the 64x64 / split-K kernels
+        if (big_tiles < DMA_MIN_TILES) return NOT_TAKEN;
         int bn = p.Cout % 128 == 0 ? 128 : 64;
-        if (force_bn == 64 || (force_bn == 0 && bn == 128 && big_tiles < 512)) bn = 64;   // more workgroups on mid-size maps
+        if (bn == 128 && big_tiles < 512) bn = 64;            // more workgroups on mid-size maps
         launch_dma_kernel(bn, KS, MODE, ctx->stream, p);
+        CR_LAUNCH_CHECK();
+        return CR_OK;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { cr_set_error("k_conv_igemm_dma launch failed: %s", hipGetErrorString(e)); *rc = CR_EHIP; }
-    else *rc = CR_OK;
-    return true;
 }
 
 // ---------------------------------------------------------------------------
@@ -1428,35 +1409,34 @@ __global__ __launch_bounds__(256) void k_conv_patch_bwd_s2_f32(ConvP p, int tile
     }
 }
 
-// true + launched if the layer takes the patch kernel
+// a patch kernel runs few long blocks: two per CU
+static constexpr int PATCH_BLOCKS_PER_CU = 2;
+
+// launched if the layer takes the patch kernel
 template <int KS, int MODE>
-static bool try_launch_conv_patch_f32(cr_ctx* ctx, const ConvP& p, int* rc) {
+static int try_launch_conv_patch_f32(cr_ctx* ctx, const ConvP& p) {
     if constexpr (KS == 1 || (KS == 7 && MODE == 1)) {
-        return false;
+        return NOT_TAKEN;
     } else {
-        static const int on = env_int("CR_CONV_PATCH", 1);
         const int cin_ok = KS == 3 ? 16 : 4;
-        if (!on || !p.f32 || p.w3 || p.cls || p.Cout != 16 || p.Cin != cin_ok || p.stride != 1 || p.pad != KS / 2 ||
+        if (!p.f32 || p.w3 || p.cls || p.Cout != 16 || p.Cin != cin_ok || p.stride != 1 || p.pad != KS / 2 ||
             p.Hin != p.Hout || p.Win != p.Wout || (p.Hout & 15) || (p.Wout & 15) || p.bias || p.relu || p.ksplit != 1 ||
             (MODE == 0 && p.res) || (MODE == 1 && p.stats))
-            return false;
+            return NOT_TAKEN;
         const int tiles_x = p.Wout / 16, tiles_per_img = tiles_x * (p.Hout / 16), tiles_total = tiles_per_img * p.N;
-        static const int per_cu = env_int("CR_CONV_PATCH_BLOCKS", 2);
-        const dim3 grid((unsigned)std::min(tiles_total, 256 * per_cu));
+        const dim3 grid((unsigned)std::min(tiles_total, 256 * PATCH_BLOCKS_PER_CU));
         if (KS == 3) hipLaunchKernelGGL((k_conv_patch_f32<3, 16, MODE>), grid, dim3(256), 0, ctx->stream, p, tiles_x, tiles_per_img, tiles_total);
         else hipLaunchKernelGGL((k_conv_patch_f32<7, 4, 0>), grid, dim3(256), 0, ctx->stream, p, tiles_x, tiles_per_img, tiles_total);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { cr_set_error("k_conv_patch_f32 launch failed: %s", hipGetErrorString(e)); *rc = CR_EHIP; }
-        else *rc = CR_OK;
-        return true;
+        CR_LAUNCH_CHECK();
+        return CR_OK;
     }
 }
 
 template <int KS, int MODE>
 static int launch_igemm_ks(cr_ctx* ctx, const ConvP& p, int out_f32) {
-    int rc_dma = CR_OK;
-    if (try_launch_conv_patch_f32<KS, MODE>(ctx, p, &rc_dma)) return rc_dma;
-    if (try_launch_dma<KS, MODE>(ctx, p, out_f32, &rc_dma)) return rc_dma;
+    int rc;
+    if ((rc = try_launch_conv_patch_f32<KS, MODE>(ctx, p)) != NOT_TAKEN) return rc;
+    if ((rc = try_launch_dma<KS, MODE>(ctx, p, out_f32)) != NOT_TAKEN) return rc;
     if (p.f32) {
         // f32 MFMA runs at 1/16 of the bf16 rate: the kernels are MFMA-bound, one wave per SIMD with >= 2 independent
         // accumulators already issues at the full rate, so the tile is chosen to put a block on every CU (intra-block
@@ -1475,20 +1455,14 @@ static int launch_igemm_ks(cr_ctx* ctx, const ConvP& p, int out_f32) {
     // the 32x32 ... 8x8 levels at 4 images/GPU give only 8-64 tiles of 128x128: use 64x64 tiles there so that the
     // launch covers the 256 CUs (MI355X: "a launch needs >> 256 workgroups")
     const int64_t big_tiles = cr_cdiv(p.M, 128) * (p.Cout >= 128 ? p.Cout / 128 : 1);
-    static const int ku_small = env_int("CR_IGEMM_KU_SMALL", 4), ku_big = env_int("CR_IGEMM_KU_BIG", 1);
-    static const int ku_tiny_blocks = env_int("CR_IGEMM_KU8_BLOCKS", 320);
     if (p.Cout % 64 == 0 && big_tiles < 512) {
         // <= ~1 block per CU: 16 waves per block on interleaved k (intra-block split-K)
-        if (cr_cdiv(p.M, 64) * (p.Cout / 64) <= ku_tiny_blocks && p.Kdim >= 512 && (KS == 1 || (p.Cin & 31) == 0))
+        constexpr int KG4_MAX_BLOCKS = 320;
+        if (cr_cdiv(p.M, 64) * (p.Cout / 64) <= KG4_MAX_BLOCKS && p.Kdim >= 512 && (KS == 1 || (p.Cin & 31) == 0))
             return launch_igemm_t<64, 64, KS, MODE, 2, 4>(ctx, p, out_f32);
-        if (ku_small == 4) return launch_igemm_t<64, 64, KS, MODE, 4>(ctx, p, out_f32);
-        if (ku_small == 2) return launch_igemm_t<64, 64, KS, MODE, 2>(ctx, p, out_f32);
-        return launch_igemm_t<64, 64, KS, MODE>(ctx, p, out_f32);
+        return launch_igemm_t<64, 64, KS, MODE, 4>(ctx, p, out_f32);
     }
-    if (p.Cout % 128 == 0) {
-        if (ku_big == 2) return launch_igemm_t<128, 128, KS, MODE, 2>(ctx, p, out_f32);
-        return launch_igemm_t<128, 128, KS, MODE>(ctx, p, out_f32);
-    }
+    if (p.Cout % 128 == 0) return launch_igemm_t<128, 128, KS, MODE>(ctx, p, out_f32);
     if (p.Cout % 64 == 0) return launch_igemm_t<128, 64, KS, MODE>(ctx, p, out_f32);
     if (p.Cout % 32 == 0) return launch_igemm_t<128, 32, KS, MODE>(ctx, p, out_f32);
     return launch_igemm_t<128, 16, KS, MODE>(ctx, p, out_f32);
@@ -1498,6 +1472,21 @@ static int ilog2_exact(int v) {
     int s = 0;
     while ((1 << s) < v) ++s;
     return ((1 << s) == v) ? s : -1;
+}
+
+// launch parameters of one convolution as an implicit GEMM over the gather source x (N x Hin x Win x Cin) into
+// y (N x Hout x Wout x Cout): no bias, residual or statistics, no k split, no parity classes, no split weights
+static ConvP make_conv_params(const void* x, const void* w, void* y, int N, int Hin, int Win, int Cin, int Hout, int Wout,
+                              int Cout, int ks, int stride, int pad, int act_f32) {
+    const size_t es = act_f32 ? 4 : 2;
+    ConvP p{};
+    p.x = x; p.w = w; p.y = y;
+    p.N = N; p.Hin = Hin; p.Win = Win; p.Cin = Cin; p.Hout = Hout; p.Wout = Wout; p.Cout = Cout;
+    p.stride = stride; p.pad = pad; p.Kdim = ks * ks * Cin; p.M = N * Hout * Wout;
+    p.cshift = ks == 1 ? 0 : ilog2_exact(Cin); p.f32 = act_f32 ? 1 : 0;
+    p.ksplit = 1; p.kstages = p.Kdim; p.Hfull = Hout; p.Wfull = Wout; p.wstride = p.Kdim;
+    p.x_bytes = (unsigned)((size_t)N * Hin * Win * Cin * es); p.w_bytes = (unsigned)((size_t)Cout * p.Kdim * es);
+    return p;
 }
 
 static int conv_common_checks(const char* who, int N, int H, int W, int Cin, int Cout, int ks, int stride, int pad,
@@ -1523,16 +1512,9 @@ extern "C" int cr_conv2d_fwd(cr_ctx* ctx, const void* x, const void* w, void* y,
     CR_CHECK_ARG(ctx && x && w && y, "cr_conv2d_fwd: NULL pointer");
     int rc = conv_common_checks("cr_conv2d_fwd", N, H, W, Cin, Cout, ks, stride, pad, act_f32);
     if (rc) return rc;
-    const size_t es = act_f32 ? 4 : 2;
-    ConvP p;
-    p.x = x; p.w = w; p.y = y; p.res = residual; p.bias = bias; p.stats = stats;
-    p.N = N; p.Hin = H; p.Win = W; p.Cin = Cin; p.Cout = Cout;
-    p.Hout = (H + 2 * pad - ks) / stride + 1;
-    p.Wout = (W + 2 * pad - ks) / stride + 1;
-    p.stride = stride; p.pad = pad; p.Kdim = ks * ks * Cin; p.M = N * p.Hout * p.Wout;
-    p.cshift = ks == 1 ? 0 : ilog2_exact(Cin); p.relu = relu; p.xcd = xcd_enabled(); p.f32 = act_f32 ? 1 : 0;
-    p.part = nullptr; p.ksplit = 1; p.kstages = p.Kdim; p.cls = 0; p.Hfull = p.Hout; p.Wfull = p.Wout; p.wstride = p.Kdim;
-    p.x_bytes = (unsigned)((size_t)N * H * W * Cin * es); p.w_bytes = (unsigned)((size_t)Cout * p.Kdim * es);
+    const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
+    ConvP p = make_conv_params(x, w, y, N, H, W, Cin, Ho, Wo, Cout, ks, stride, pad, act_f32);
+    p.res = residual; p.bias = bias; p.stats = stats; p.relu = relu;
     p.w3 = (act_f32 == 2 && (p.Kdim & 31) == 0) ? w_split : nullptr; p.w3_bytes = (unsigned)((size_t)Cout * p.Kdim * 6);
     if (act_f32) out_f32 = 1;
     if (ks == 1) return launch_igemm_ks<1, 0>(ctx, p, out_f32);
@@ -1549,29 +1531,20 @@ extern "C" int cr_conv2d_bwd_data(cr_ctx* ctx, const void* dy, const void* wt, v
     int rc = conv_common_checks("cr_conv2d_bwd_data", N, H, W, Cout, Cin, ks, stride, pad, act_f32);
     if (rc) return rc;
     CR_CHECK_ARG(Cin % 16 == 0, "cr_conv2d_bwd_data: Cin=%d must be a multiple of 16", Cin);
-    const size_t es = act_f32 ? 4 : 2;
-    ConvP p;
     const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
-    p.x = dy; p.w = wt; p.y = dx; p.res = accumulate; p.bias = nullptr; p.stats = nullptr;   // res: dx = conv^T(dy) + accumulate
-    p.N = N; p.Hin = Ho; p.Win = Wo; p.Cin = Cout;      // gather source = dY
-    p.Hout = H; p.Wout = W; p.Cout = Cin;               // GEMM output = dX
-    p.stride = stride; p.pad = pad; p.Kdim = ks * ks * Cout; p.M = N * H * W;
-    p.cshift = ks == 1 ? 0 : ilog2_exact(Cout); p.relu = 0; p.xcd = xcd_enabled(); p.f32 = act_f32 ? 1 : 0;
-    p.part = nullptr; p.ksplit = 1; p.kstages = p.Kdim; p.cls = 0; p.Hfull = p.Hout; p.Wfull = p.Wout; p.wstride = p.Kdim;
-    p.x_bytes = (unsigned)((size_t)N * Ho * Wo * Cout * es); p.w_bytes = (unsigned)((size_t)Cin * p.Kdim * es);
+    // gather source = dY (Ho x Wo x Cout), GEMM output = dX (H x W x Cin)
+    ConvP p = make_conv_params(dy, wt, dx, N, Ho, Wo, Cout, H, W, Cin, ks, stride, pad, act_f32);
+    p.res = accumulate;                                 // dx = conv^T(dy) + accumulate
     p.w3 = (act_f32 == 2 && (p.Kdim & 31) == 0) ? wt_split : nullptr; p.w3_bytes = (unsigned)((size_t)Cin * p.Kdim * 6);
-    static const int patch_s2 = env_int("CR_CONV_PATCH", 1);
-    if (patch_s2 && act_f32 && stride == 2 && ks == 3 && pad == 1 && Cout == 32 && Cin == 16 && (H & 15) == 0 && (W & 15) == 0 &&
+    if (act_f32 && stride == 2 && ks == 3 && pad == 1 && Cout == 32 && Cin == 16 && (H & 15) == 0 && (W & 15) == 0 &&
         Ho * 2 == H && Wo * 2 == W) {
         const int tiles_x = W / 16, tiles_per_img = tiles_x * (H / 16), tiles_total = tiles_per_img * N;
-        static const int per_cu = env_int("CR_CONV_PATCH_BLOCKS", 2);
-        const dim3 grid((unsigned)std::min(tiles_total, 256 * per_cu));
+        const dim3 grid((unsigned)std::min(tiles_total, 256 * PATCH_BLOCKS_PER_CU));
         hipLaunchKernelGGL(k_conv_patch_bwd_s2_f32, grid, dim3(256), 0, ctx->stream, p, tiles_x, tiles_per_img, tiles_total);
         CR_LAUNCH_CHECK();
         return CR_OK;
     }
-    static const int cls_on = env_int("CR_BWD_S2_CLASSES", 1);
-    if (cls_on && stride == 2 && ks == 3 && (H & 1) == 0 && (W & 1) == 0 && (Cout & (act_f32 ? 15 : 31)) == 0) {
+    if (stride == 2 && ks == 3 && (H & 1) == 0 && (W & 1) == 0 && (Cout & (act_f32 ? 15 : 31)) == 0) {
         // by output-pixel parity class (see ConvP): H/2 x W/2 pixels per class, 4 classes in one grid
         p.cls = 1; p.Hfull = H; p.Wfull = W;
         p.Hout = H / 2; p.Wout = W / 2; p.M = N * p.Hout * p.Wout;
@@ -1594,22 +1567,21 @@ static int group_starts(int n, const int* counts, int* starts) {
 // k_splitk_epilogue in a fixed order), so the last round is made of 1/S-duration blocks: 1 024 + 3 x 340 blocks = 2 + 2/3 rounds.
 // f32 only (bf16 tiles are 6 x shorter: the epilogue launches would cost more than the partial round).  Returns the number of
 // problems that were split; their indices are the trailing ones of `split[]`.
+static constexpr int GRP_KSPLIT = 3;          // also for groups under half a round (4 / 5 ways there measured +0.05 ms per step)
 static int group_tail_split(cr_ctx* ctx, ConvGroup& g, int* counts, int n, bool* split) {
-    static const int S_env = env_int("CR_GRP_KSPLIT", 3);
     for (int i = 0; i < n; ++i) split[i] = false;
-    if (S_env < 2 || !ctx->ws) return 0;
+    if (!ctx->ws) return 0;
     const int slots = 512;
     int total = 0;
     for (int i = 0; i < n; ++i) total += counts[i];
     const int full = (total / slots) * slots, rem = total - full;
     int bulk = 0, nsplit = 0;
     size_t need = 0;
-    int S = S_env;
+    int S = GRP_KSPLIT;
     if (total * 2 <= slots) {
         // a group that fills less than half of ONE round (the three small FPN levels: 88 tiles on 256 CUs): every problem is
         // split along k, as many ways as still fit the resident slots
-        static const int S_small = env_int("CR_GRP_KSPLIT_SMALL", 3);
-        S = S_small < slots / total ? S_small : slots / total;
+        S = GRP_KSPLIT < slots / total ? GRP_KSPLIT : slots / total;
         if (S < 2) return 0;
         for (int i = 0; i < n; ++i) {
             split[i] = true;
@@ -1662,7 +1634,6 @@ extern "C" int cr_conv2d_fwd_group(cr_ctx* ctx, int n, const void* const* xs, co
     CR_CHECK_ARG(n >= 1 && n <= CR_MAX_GROUP, "cr_conv2d_fwd_group: 1..%d problems", CR_MAX_GROUP);
     CR_CHECK_ARG((ks == 1 || ks == 3) && act_f32 != 2 && Cout % 128 == 0 && (Cin & (act_f32 ? 31 : 63)) == 0,
                  "cr_conv2d_fwd_group: k in {1,3}, Cout %% 128 == 0, Cin %% 64 (32 in f32) == 0, fp32 or bf16");
-    const size_t es = act_f32 ? 4 : 2;
     ConvGroup g;
     int counts[CR_MAX_GROUP];
     g.n = n;
@@ -1670,16 +1641,10 @@ extern "C" int cr_conv2d_fwd_group(cr_ctx* ctx, int n, const void* const* xs, co
         CR_CHECK_ARG(xs[i] && ws[i] && ys[i], "cr_conv2d_fwd_group: NULL tensor %d", i);
         int rc = conv_common_checks("cr_conv2d_fwd_group", Ns[i], Hs[i], Ws[i], Cin, Cout, ks, 1, pad, act_f32);
         if (rc) return rc;
+        const int H = Hs[i], W = Ws[i], Ho = H + 2 * pad - ks + 1, Wo = W + 2 * pad - ks + 1;
         ConvP& p = g.p[i];
-        p.x = xs[i]; p.w = ws[i]; p.y = ys[i]; p.res = residuals ? residuals[i] : nullptr; p.bias = biases ? biases[i] : nullptr;
-        p.stats = nullptr;
-        p.N = Ns[i]; p.Hin = Hs[i]; p.Win = Ws[i]; p.Cin = Cin; p.Cout = Cout;
-        p.Hout = Hs[i] + 2 * pad - ks + 1; p.Wout = Ws[i] + 2 * pad - ks + 1;
-        p.stride = 1; p.pad = pad; p.Kdim = ks * ks * Cin; p.M = p.N * p.Hout * p.Wout;
-        p.cshift = ks == 1 ? 0 : ilog2_exact(Cin); p.relu = relu; p.xcd = xcd_enabled(); p.f32 = act_f32 ? 1 : 0;
-        p.part = nullptr; p.ksplit = 1; p.kstages = p.Kdim; p.cls = 0; p.Hfull = p.Hout; p.Wfull = p.Wout; p.wstride = p.Kdim;
-        p.x_bytes = (unsigned)((size_t)p.N * p.Hin * p.Win * Cin * es); p.w_bytes = (unsigned)((size_t)Cout * p.Kdim * es);
-        p.w3 = nullptr; p.w3_bytes = 0;
+        p = make_conv_params(xs[i], ws[i], ys[i], Ns[i], H, W, Cin, Ho, Wo, Cout, ks, 1, pad, act_f32);
+        p.res = residuals ? residuals[i] : nullptr; p.bias = biases ? biases[i] : nullptr; p.relu = relu;
         counts[i] = (int)(cr_cdiv(p.M, 128) * (Cout / 128));
     }
     bool split[CR_MAX_GROUP];
@@ -1714,13 +1679,7 @@ extern "C" int cr_gemm_batched_f32(cr_ctx* ctx, const float* x, const float* w, 
     CR_CHECK_ARG(O % 128 == 0 && K % 32 == 0, "cr_gemm_batched_f32: O %% 128 == 0, K %% 32 == 0");
     int rc = conv_common_checks("cr_gemm_batched_f32", 1, 1, R, K, O, 1, 1, 0, 1);
     if (rc) return rc;
-    ConvP p;
-    p.x = x; p.w = w; p.y = y; p.res = nullptr; p.bias = nullptr; p.stats = nullptr;
-    p.N = 1; p.Hin = 1; p.Win = R; p.Cin = K; p.Cout = O; p.Hout = 1; p.Wout = R;
-    p.stride = 1; p.pad = 0; p.Kdim = K; p.M = R; p.cshift = 0; p.relu = 0; p.xcd = xcd_enabled(); p.f32 = 1;
-    p.part = nullptr; p.ksplit = 1; p.kstages = p.Kdim; p.cls = 0; p.Hfull = 1; p.Wfull = R; p.wstride = K;
-    p.x_bytes = (unsigned)((size_t)R * K * 4); p.w_bytes = (unsigned)((size_t)O * K * 4);
-    p.w3 = nullptr; p.w3_bytes = 0;
+    const ConvP p = make_conv_params(x, w, y, 1, 1, R, K, 1, R, O, 1, 1, 0, 1);    // a 1 x R image of K channels, 1x1 filter
     const int count = (int)(cr_cdiv(R, 128) * (O / 128));
     hipLaunchKernelGGL(k_gemm_batched_f32, dim3((unsigned)count, (unsigned)batches), dim3(CONV_T), 0, ctx->stream, p,
                        (long long)stride_x, (long long)stride_w, (long long)stride_y, count);
@@ -1736,7 +1695,6 @@ extern "C" int cr_conv2d_bwd_data_group(cr_ctx* ctx, int n, const void* const* d
     CR_CHECK_ARG(n >= 1 && n <= CR_MAX_GROUP, "cr_conv2d_bwd_data_group: 1..%d problems", CR_MAX_GROUP);
     CR_CHECK_ARG((ks == 1 || ks == 3) && act_f32 != 2 && Cin % 128 == 0 && (Cout & (act_f32 ? 31 : 63)) == 0,
                  "cr_conv2d_bwd_data_group: k in {1,3}, Cin %% 128 == 0, Cout %% 64 (32 in f32) == 0, fp32 or bf16");
-    const size_t es = act_f32 ? 4 : 2;
     ConvGroup g;
     int counts[CR_MAX_GROUP];
     g.n = n;
@@ -1746,14 +1704,9 @@ extern "C" int cr_conv2d_bwd_data_group(cr_ctx* ctx, int n, const void* const* d
         if (rc) return rc;
         const int H = Hs[i], W = Ws[i], Ho = H + 2 * pad - ks + 1, Wo = W + 2 * pad - ks + 1;
         ConvP& p = g.p[i];
-        p.x = dys[i]; p.w = wts[i]; p.y = dxs[i]; p.res = accumulates ? accumulates[i] : nullptr; p.bias = nullptr; p.stats = nullptr;
-        p.N = Ns[i]; p.Hin = Ho; p.Win = Wo; p.Cin = Cout;      // gather source = dY
-        p.Hout = H; p.Wout = W; p.Cout = Cin;                   // GEMM output = dX
-        p.stride = 1; p.pad = pad; p.Kdim = ks * ks * Cout; p.M = p.N * H * W;
-        p.cshift = ks == 1 ? 0 : ilog2_exact(Cout); p.relu = 0; p.xcd = xcd_enabled(); p.f32 = act_f32 ? 1 : 0;
-        p.part = nullptr; p.ksplit = 1; p.kstages = p.Kdim; p.cls = 0; p.Hfull = H; p.Wfull = W; p.wstride = p.Kdim;
-        p.x_bytes = (unsigned)((size_t)p.N * Ho * Wo * Cout * es); p.w_bytes = (unsigned)((size_t)Cin * p.Kdim * es);
-        p.w3 = nullptr; p.w3_bytes = 0;
+        // gather source = dY (Ho x Wo x Cout), GEMM output = dX (H x W x Cin)
+        p = make_conv_params(dys[i], wts[i], dxs[i], Ns[i], Ho, Wo, Cout, H, W, Cin, ks, 1, pad, act_f32);
+        p.res = accumulates ? accumulates[i] : nullptr;
         counts[i] = (int)(cr_cdiv(p.M, 128) * (Cin / 128));
     }
     bool split[CR_MAX_GROUP];
@@ -1781,10 +1734,9 @@ struct WgP {
     float* dw;       // [Cout][Kdim] f32, accumulated with atomics
     int N, Hin, Win, Cin, Hout, Wout, Cout, stride, pad, Kdim, M, cshift;
     int steps_per_split;    // 32-pixel steps handled by one split
-    int tm, tn, xcd;        // tile counts (the grid is 1-D: tm * tn * splits blocks)
+    int tm, tn;             // tile counts (the grid is 1-D: tm * tn * splits blocks)
     unsigned x_bytes, dy_bytes;   // extents for the buffer-load descriptors
     float* dbias;           // optional [Cout]: += column sums of dy (bias gradient), accumulated by the first k-tile's blocks
-    int dbg;                // tuning only (CR_S3_DBG): 1 = no MFMAs, 2 = no LDS fragment reads either, 4 = no atomics
     int cshift_w;           // log2(Wout) (k_conv_wgrad_s3_row)
     int cshift_hw;          // log2(Hout * Wout) or -1
     // deterministic mode (CR_DETERMINISTIC=1, f32 kernels): pixel split s writes ITS sum of every dW / bias element to
@@ -1806,6 +1758,20 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ 
 static bool deterministic_on() {
     static const int v = getenv("CR_DETERMINISTIC") ? atoi(getenv("CR_DETERMINISTIC")) : 0;
     return v != 0;
+}
+
+// launch parameters of one weight gradient of dY (N x Hout x Wout x Cout) against the gather source x (N x Hin x Win x Cin):
+// no bias gradient, no slabs; the launcher sets the pixel split and the tile counts
+static WgP make_wgrad_params(const void* dy, const void* x, float* dw, int N, int Hin, int Win, int Cin, int Hout, int Wout,
+                             int Cout, int ks, int stride, int pad, int act_f32) {
+    const size_t es = act_f32 ? 4 : 2;
+    WgP p{};
+    p.dy = dy; p.x = x; p.dw = dw;
+    p.N = N; p.Hin = Hin; p.Win = Win; p.Cin = Cin; p.Hout = Hout; p.Wout = Wout; p.Cout = Cout;
+    p.stride = stride; p.pad = pad; p.Kdim = ks * ks * Cin; p.M = N * Hout * Wout;
+    p.cshift = ks == 1 ? 0 : ilog2_exact(Cin); p.cshift_hw = -1;
+    p.x_bytes = (unsigned)((size_t)N * Hin * Win * Cin * es); p.dy_bytes = (unsigned)((size_t)p.M * Cout * es);
+    return p;
 }
 
 // points p at slabs in the ctx workspace (at byte offset `off`, advanced) for `splits` pixel splits; false = does not fit
@@ -1865,7 +1831,7 @@ __global__ __launch_bounds__(CONV_T * KG) void k_conv_wgrad(WgP p) {
 
     const int tid = threadIdx.x & (CONV_T - 1), lane = tid & 63, wave = tid >> 6;
     // 1-D grid, channel tile fastest, split slowest: all tiles of one split (same pixel range) are neighbours
-    const int bid = p.xcd ? xcd_swizzle(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
     const int bx = bid % p.tm, by = (bid / p.tm) % p.tn, bz = bid / (p.tm * p.tn);
     const int c0 = bx * TM;                // output-channel tile
     const int q0 = by * TN;                // k (r,s,c) tile
@@ -2070,7 +2036,7 @@ __device__ __forceinline__ void conv_wgrad_f32_body(const WgP& p, const int blk_
     (void)xg;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int bid = p.xcd ? xcd_swizzle(blk_id, blk_count) : blk_id;
+    const int bid = xcd_swizzle(blk_id, blk_count);
     const int bx = bid % p.tm, by = (bid / p.tm) % p.tn, bz = bid / (p.tm * p.tn);
     const int c0 = bx * TM, q0 = by * TN;
     const int step0 = bz * p.steps_per_split;            // steps are PS pixels here
@@ -2392,26 +2358,22 @@ __global__ __launch_bounds__(256) void k_conv_wgrad_patch_f32(WgP p, int tiles_x
     }
 }
 
-// true + launched if the layer takes the patch kernel
-static bool try_launch_wgrad_patch_f32(cr_ctx* ctx, WgP& p, int ks, int* rc) {
-    static const int on = env_int("CR_WG_PATCH", 1);
+// launched if the layer takes the patch kernel
+static int try_launch_wgrad_patch_f32(cr_ctx* ctx, WgP& p, int ks) {
     const bool shape_ok = p.Cout == 16 && p.stride == 1 && p.pad == ks / 2 && (p.Hout & 15) == 0 && (p.Wout & 15) == 0 &&
                           p.Hin == p.Hout && p.Win == p.Wout && ((ks == 3 && p.Cin == 16) || (ks == 7 && p.Cin == 4));
-    if (!on || !shape_ok) return false;
+    if (!shape_ok) return NOT_TAKEN;
     const int tiles_x = p.Wout / 16, tiles_per_img = tiles_x * (p.Hout / 16), tiles_total = tiles_per_img * p.N;
-    static const int per_cu = env_int("CR_WG_PATCH_BLOCKS", 2);       // few long blocks: the prologue / epilogue of all blocks coincide
-    const dim3 grid((unsigned)std::min(tiles_total, 256 * per_cu));   // block b: tiles b, b + grid, ...
+    // few long blocks: the prologue / epilogue of all blocks coincide
+    const dim3 grid((unsigned)std::min(tiles_total, 256 * PATCH_BLOCKS_PER_CU));   // block b: tiles b, b + grid, ...
     size_t ws_off = 0;
-    float* const db = p.dbias;
-    if (deterministic_on() && db) return false;                       // (bias on this kernel stays on atomics: generic kernel instead)
+    if (deterministic_on() && p.dbias) return NOT_TAKEN;                      // (bias on this kernel stays on atomics: generic kernel instead)
     const bool slabs = wgrad_use_slabs(ctx, p, (int)grid.x, &ws_off);
     if (ks == 3) hipLaunchKernelGGL((k_conv_wgrad_patch_f32<3, 16>), grid, dim3(256), 0, ctx->stream, p, tiles_x, tiles_per_img, tiles_total);
     else hipLaunchKernelGGL((k_conv_wgrad_patch_f32<7, 4>), grid, dim3(256), 0, ctx->stream, p, tiles_x, tiles_per_img, tiles_total);
     if (slabs) wgrad_reduce_slabs(ctx, p, (int)grid.x);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { cr_set_error("k_conv_wgrad_patch_f32 launch failed: %s", hipGetErrorString(e)); *rc = CR_EHIP; }
-    else *rc = CR_OK;
-    return true;
+    CR_LAUNCH_CHECK();
+    return CR_OK;
 }
 
 template <int KS>
@@ -2419,10 +2381,8 @@ static int launch_wgrad_f32_ks(cr_ctx* ctx, WgP& p) {
     constexpr int PS = 16;
     const int nsteps = (p.M + PS - 1) / PS;
     const int tn = (int)cr_cdiv(p.Kdim, 128);
-    static const int tm_cap = env_int("CR_WG_F32_TM", 128);
     int TM = p.Cout >= 128 ? 128 : (p.Cout >= 64 ? 64 : (p.Cout >= 32 ? 32 : 16));
-    if (TM > tm_cap) TM = tm_cap;
-    // measured (scripts/wgrad_mid_tune.py): 64-channel tiles (twice the tiles, half the pixel splits and atomics) win on the
+    // measured: 64-channel tiles (twice the tiles, half the pixel splits and atomics) win on the
     // 64x64 maps with 128 channels (69.7 -> 61.6 us) and the 32x32 maps with 256 (66.7 -> 60.1), lose elsewhere
     if (TM == 128 && ((p.Cout == 128 && p.M <= 16384) || (p.Cout == 256 && p.M <= 4096))) TM = 64;
     // the RoI heads' FC layers (1024 outputs, <= 2048 rows; scripts/fc_bench.py): 64-row tiles, 63 -> 52 us (1024 x 1024),
@@ -2430,29 +2390,26 @@ static int launch_wgrad_f32_ks(cr_ctx* ctx, WgP& p) {
     if (TM == 128 && KS == 1 && p.Cout >= 1024) TM = 64;
     const int tm = (int)cr_cdiv(p.Cout, TM);
     const int tiles = tm * tn;
-    // Split the pixel range over blocks.  Measured on the 3x3 256->256 layers (scripts/wgrad_f32_tune.py): one block per CU
+    // Split the pixel range over blocks.  Measured on the 3x3 256->256 layers: one block per CU
     // (one wave per SIMD) exposes the LDS / barrier latencies (92 TFLOP/s), two reach 110, three 114; a block count just
     // ABOVE a multiple of the 256 CUs runs at the speed of the next multiple (792 blocks: 92).  So: the largest split count
     // that keeps the grid <= 3 x 256 blocks, every block keeping >= 8 sub-steps (128 pixels) to hide its atomics behind.
-    static const int force_splits = env_int("CR_WG_SPLITS_F32", 0);
     const int max_splits = nsteps / 8 > 1 ? nsteps / 8 : 1;
     int splits = 768 / tiles;
     // more tiles than the chip holds at once (12544 x 1024: 1568): the grid is a little over a whole number of rounds and
     // the last few blocks cost a round of their own; halving the blocks halves that tail (567 -> 480 us)
     if (tiles > 768 && nsteps >= 32) splits = 2;
     if (splits > max_splits) splits = max_splits;
-    if (force_splits > 0) splits = force_splits;
     if (splits > nsteps) splits = nsteps;
     if (splits < 1) splits = 1;
     p.steps_per_split = (nsteps + splits - 1) / splits;
     p.steps_per_split = (p.steps_per_split + 1) & ~1;            // whole stages (KU = 2 sub-steps)
     splits = (nsteps + p.steps_per_split - 1) / p.steps_per_split;
     dim3 grid(tm * tn * splits);
-    p.tm = tm; p.tn = tn; p.xcd = xcd_enabled();
+    p.tm = tm; p.tn = tn;
     size_t ws_off = 0;
     const bool slabs = wgrad_use_slabs(ctx, p, splits, &ws_off);
-    static const int lds_pad = env_int("CR_WG_F32_LDS_PAD", 0);     // extra dynamic LDS per block: caps the blocks per CU (tuning)
-    if (TM == 128) hipLaunchKernelGGL((k_conv_wgrad_f32<128, KS>), grid, dim3(CONV_T), lds_pad, ctx->stream, p);
+    if (TM == 128) hipLaunchKernelGGL((k_conv_wgrad_f32<128, KS>), grid, dim3(CONV_T), 0, ctx->stream, p);
     else if (TM == 64) hipLaunchKernelGGL((k_conv_wgrad_f32<64, KS>), grid, dim3(CONV_T), 0, ctx->stream, p);
     else if (TM == 32) hipLaunchKernelGGL((k_conv_wgrad_f32<32, KS>), grid, dim3(CONV_T), 0, ctx->stream, p);
     else hipLaunchKernelGGL((k_conv_wgrad_f32<16, KS>), grid, dim3(CONV_T), 0, ctx->stream, p);
@@ -2491,7 +2448,7 @@ __global__ __launch_bounds__(CONV_T * 2) void k_conv_wgrad_s3(WgP p) {
     u16* sQ = sP + 3 * PE;                               // planes at sQ + pl * QE
 
     const int tid = threadIdx.x & (CONV_T - 1), lane = tid & 63, wave = tid >> 6;
-    const int bid = p.xcd ? xcd_swizzle(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
     const int bx = bid % p.tm, by = (bid / p.tm) % p.tn, bz = bid / (p.tm * p.tn);
     const int c0 = bx * TM, q0 = by * TN;
     const int step0 = bz * p.steps_per_split;
@@ -2623,15 +2580,13 @@ __global__ __launch_bounds__(CONV_T * 2) void k_conv_wgrad_s3(WgP p) {
                 const s16x4 lo = lds_tr16(b0), hi = lds_tr16(b0 + 4 * PQ);
                 bfr[j] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
             }
-            if (!(p.dbg & 1)) {
 #pragma unroll
-                for (int pa = 2 - pb; pa >= 0; --pa)
+            for (int pa = 2 - pb; pa >= 0; --pa)
 #pragma unroll
-                    for (int i = 0; i < TI; ++i)
+                for (int i = 0; i < TI; ++i)
 #pragma unroll
-                        for (int j = 0; j < TJ; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[pa][i], bfr[j], acc[i][j], 0, 0, 0);
-            }
+                    for (int j = 0; j < TJ; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[pa][i], bfr[j], acc[i][j], 0, 0, 0);
         }
     };
 
@@ -2660,7 +2615,6 @@ __global__ __launch_bounds__(CONV_T * 2) void k_conv_wgrad_s3(WgP p) {
         if (i + 1 < nst) phase_pair(i + 1, S1{}, S0{});
     }
     if (do_bias && c0 + tid < p.Cout) atomicAdd(&p.dbias[c0 + tid], bsum);
-    if (p.dbg & 4) { if (acc[0][0][0] == 123.456f) p.dw[0] = 1.f; return; }
     // sum the two groups' accumulators in LDS (the operand images are dead: the loop ended with a barrier), then one set
     // of atomics per block, full 512-B rows per wave-instruction.  D: col (lane&15) = k index, row 4(lane>>4)+reg = channel
     float* tile = reinterpret_cast<float*>(smem);
@@ -2710,7 +2664,7 @@ __global__ __launch_bounds__(CONV_T * 2) void k_conv_wgrad_s3_row(WgP p) {
     auto rot = [](int row, int col) { return (col + (((row >> 3) & 1) << 6)) & 127; };
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int bid = p.xcd ? xcd_swizzle(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
     const int bx = bid % p.tm, by = (bid / p.tm) % p.tn, bz = bid / (p.tm * p.tn);
     const int c0 = bx * TM;
     const int nhalf = p.Cin >> 7;
@@ -2887,74 +2841,63 @@ __global__ __launch_bounds__(CONV_T * 2) void k_conv_wgrad_s3_row(WgP p) {
         }
 }
 
-static bool try_launch_wgrad_s3_row(cr_ctx* ctx, WgP& p, int* rc) {
-    static const int on = env_int("CR_S3_WGRAD_ROW", 1);
+static int try_launch_wgrad_s3_row(cr_ctx* ctx, WgP& p) {
     const int W = p.Wout;
-    if (!on || p.stride != 1 || p.pad != 1 || (p.Cin & 127) || (p.Cout & 127) || W < 8 || (W & (W - 1)) || (p.M & 31) ||
+    if (p.stride != 1 || p.pad != 1 || (p.Cin & 127) || (p.Cout & 127) || W < 8 || (W & (W - 1)) || (p.M & 31) ||
         p.Hin != p.Hout || p.Win != p.Wout || p.M < 1024)
-        return false;
+        return NOT_TAKEN;
     const int nsteps = p.M >> 5;
     const int tm = p.Cout / 128, tn = 3 * (p.Cin / 128);
     const int tiles = tm * tn;
-    static const int force_splits = env_int("CR_WG_SPLITS_S3R", 0), target = env_int("CR_WG_S3R_BLOCKS", 256);
-    int splits = target / tiles;
+    constexpr int TARGET_BLOCKS = 256;                // one block per CU
+    int splits = TARGET_BLOCKS / tiles;
     // A row tile is three 128 x 128 tiles: the grid needs three times the pixel splits of k_conv_wgrad_s3 to fill the chip,
     // each with a 128 x 384 set of atomics.  Measured (scripts/conv_shapes_bench.py, fp32x3): it pays on the 4x128x128x256
     // layers (0.65 -> 0.47 ms in the step) and loses on the 64x64 and smaller maps (70 vs 43 us on 3x3 128->128), i.e. it needs
     // >= 64 steps per block to amortise them.
-    static const int min_steps = env_int("CR_WG_S3R_MIN_STEPS", 64);
-    if (splits < 1 || nsteps / splits < min_steps) return false;
-    if (force_splits > 0) splits = force_splits;
+    constexpr int MIN_STEPS = 64;
+    if (splits < 1 || nsteps / splits < MIN_STEPS) return NOT_TAKEN;
     if (splits > nsteps) splits = nsteps;
     p.steps_per_split = (nsteps + splits - 1) / splits;
     splits = (nsteps + p.steps_per_split - 1) / p.steps_per_split;
-    p.tm = tm; p.tn = tn; p.xcd = xcd_enabled();
+    p.tm = tm; p.tn = tn;
     p.cshift_w = ilog2_exact(W);
     p.cshift_hw = ilog2_exact(p.Hout * W);            // -1: the image size is not a power of two (division per window row)
     constexpr size_t LDS = 2 * 3 * (32 * 144 + 36 * 144) * sizeof(u16);
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t ea = hipFuncSetAttribute((const void*)k_conv_wgrad_s3_row, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-        if (ea != hipSuccess) { cr_set_error("k_conv_wgrad_s3_row: LDS attribute: %s", hipGetErrorString(ea)); *rc = CR_EHIP; return true; }
+        CR_HIP(hipFuncSetAttribute((const void*)k_conv_wgrad_s3_row, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
         attr_done = true;
     }
     hipLaunchKernelGGL(k_conv_wgrad_s3_row, dim3((unsigned)(tiles * splits)), dim3(CONV_T * 2), LDS, ctx->stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { cr_set_error("k_conv_wgrad_s3_row launch failed: %s", hipGetErrorString(e)); *rc = CR_EHIP; }
-    else *rc = CR_OK;
-    return true;
+    CR_LAUNCH_CHECK();
+    return CR_OK;
 }
 
-// true + launched when the layer takes the split-mode weight-gradient kernel
+// launched when the layer takes the split-mode weight-gradient kernel
 template <int KS>
-static bool try_launch_wgrad_s3(cr_ctx* ctx, WgP& p, int* rc) {
-    static const int on = env_int("CR_S3_WGRAD", 1);
-    if (!on || p.Cout < 64 || (p.Cout & 7) || (p.Cin & 7) || p.M < 512) return false;
+static int try_launch_wgrad_s3(cr_ctx* ctx, WgP& p) {
+    if (p.Cout < 64 || (p.Cout & 7) || (p.Cin & 7) || p.M < 512) return NOT_TAKEN;
     const int nsteps = (p.M + 31) >> 5;
     const int tn = (int)cr_cdiv(p.Kdim, 128);
     const int TM = p.Cout >= 128 ? 128 : 64;
     const int tm = (int)cr_cdiv(p.Cout, TM);
     const int tiles = tm * tn;
     // 110 KB of LDS per block of 8 waves: one block per CU; every block keeps >= 8 steps (4 per group)
-    static const int force_splits = env_int("CR_WG_SPLITS_S3", 0), target = env_int("CR_WG_S3_BLOCKS", 256);
-    int splits = target / tiles;
+    constexpr int TARGET_BLOCKS = 256;
+    int splits = TARGET_BLOCKS / tiles;
     if (splits > nsteps / 8) splits = nsteps / 8;
-    if (force_splits > 0) splits = force_splits;
     if (splits > nsteps) splits = nsteps;
     if (splits < 1) splits = 1;
     p.steps_per_split = (nsteps + splits - 1) / splits;
     p.steps_per_split = (p.steps_per_split + 1) & ~1;             // whole step pairs (one step per group)
     splits = (nsteps + p.steps_per_split - 1) / p.steps_per_split;
     dim3 grid(tm * tn * splits);
-    p.tm = tm; p.tn = tn; p.xcd = xcd_enabled();
-    static const int dbg = env_int("CR_S3_DBG", 0);
-    p.dbg = dbg;
+    p.tm = tm; p.tn = tn;
     if (TM == 128) hipLaunchKernelGGL((k_conv_wgrad_s3<128, KS>), grid, dim3(CONV_T * 2), 0, ctx->stream, p);
     else hipLaunchKernelGGL((k_conv_wgrad_s3<64, KS>), grid, dim3(CONV_T * 2), 0, ctx->stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { cr_set_error("k_conv_wgrad_s3 launch failed: %s", hipGetErrorString(e)); *rc = CR_EHIP; }
-    else *rc = CR_OK;
-    return true;
+    CR_LAUNCH_CHECK();
+    return CR_OK;
 }
 
 template <int KS>
@@ -2962,21 +2905,17 @@ static int launch_wgrad_ks(cr_ctx* ctx, WgP& p) {
     const int nsteps = (p.M + 31) >> 5;
     const int tn = (int)cr_cdiv(p.Kdim, 128);
     int TM = p.Cout >= 128 ? 128 : (p.Cout >= 64 ? 64 : (p.Cout >= 32 ? 32 : 16));
-    // wave groups per block (intra-block split over pixels): 0 = decide below
-    static const int force_kg = env_int("CR_WG_KG", 0);
-    int kg = force_kg;
-    if (kg <= 0) {      // measured per layer shape (scripts/conv_shapes_bench.py, CR_WG_KG sweep)
-        const int64_t dw_elems = (int64_t)p.Cout * p.Kdim;
-        if (p.M >= 1024 && p.Cout >= 64 && dw_elems <= 160 * 1024) kg = 4;
-        else if (p.M >= 1024 && p.M <= 4096 && p.Cout >= 128) kg = 2;
-        else kg = 1;
-    }
-    if (kg == 4 && TM == 128) TM = 64;              // 16 waves per block: 128 registers per lane
+    // wave groups per block (intra-block split over pixels), measured per layer shape (scripts/conv_shapes_bench.py)
+    const int64_t dw_elems = (int64_t)p.Cout * p.Kdim;
+    int kg = 1;
+    if (p.M >= 1024 && p.Cout >= 64 && dw_elems <= 160 * 1024) kg = 4;
+    else if (p.M >= 1024 && p.M <= 4096 && p.Cout >= 128) kg = 2;
+    if (kg == 4) TM = 64;                           // (Cout >= 64) 16 waves per block: 128 registers per lane
     if (kg == 2 && TM != 128) kg = 1;
     const int tm = (int)cr_cdiv(p.Cout, TM);
     // Split the pixel range over blockIdx.z.  Every split adds one full set of f32 atomics over dW (1.3 TB/s on
     // MI355X), so the split count is bounded by ~16 pixel steps (512 pixels) of MFMA work per block and by the number
-    // of blocks the chip holds at once (measured per layer shape with scripts/conv_shapes_bench.py, CR_WG_SPLITS sweep).
+    // of blocks the chip holds at once (measured per layer shape with scripts/conv_shapes_bench.py).
     const int tiles = tm * tn;
     const int block_cap = TM >= 64 ? 576 : 2048;
     int splits = nsteps / (16 * kg);
@@ -2996,18 +2935,14 @@ static int launch_wgrad_ks(cr_ctx* ctx, WgP& p) {
         if (s2 > 256 / tiles) s2 = 256 / tiles;
         if (s2 > splits) splits = s2;
     }
-    static const int force_splits = env_int("CR_WG_SPLITS", 0);
-    if (force_splits > 0) splits = force_splits;
     if (splits > nsteps) splits = nsteps;
     if (splits < 1) splits = 1;
     p.steps_per_split = (nsteps + splits - 1) / splits;
     splits = (nsteps + p.steps_per_split - 1) / p.steps_per_split;
     dim3 grid(tm * tn * splits);
-    p.tm = tm; p.tn = tn; p.xcd = xcd_enabled();
+    p.tm = tm; p.tn = tn;
     if (kg == 4) {
-        if (TM == 64) hipLaunchKernelGGL((k_conv_wgrad<64, KS, 2, 4>), grid, dim3(CONV_T * 4), 0, ctx->stream, p);
-        else if (TM == 32) hipLaunchKernelGGL((k_conv_wgrad<32, KS, 2, 4>), grid, dim3(CONV_T * 4), 0, ctx->stream, p);
-        else hipLaunchKernelGGL((k_conv_wgrad<16, KS, 2, 4>), grid, dim3(CONV_T * 4), 0, ctx->stream, p);
+        hipLaunchKernelGGL((k_conv_wgrad<64, KS, 2, 4>), grid, dim3(CONV_T * 4), 0, ctx->stream, p);
     } else if (kg == 2) {
         hipLaunchKernelGGL((k_conv_wgrad<128, KS, 2, 2>), grid, dim3(CONV_T * 2), 0, ctx->stream, p);
     } else {
@@ -3032,33 +2967,19 @@ static int conv2d_bwd_weight_impl(cr_ctx* ctx, const void* dy, const void* x, fl
     CR_CHECK_ARG(ctx && dy && x && dw, "cr_conv2d_bwd_weight: NULL pointer");
     int rc = conv_common_checks("cr_conv2d_bwd_weight", N, H, W, Cin, Cout, ks, stride, pad, act_f32);
     if (rc) return rc;
-    const size_t es = act_f32 ? 4 : 2;
-    WgP p;
-    p.dbg = 0; p.cshift_w = 0; p.cshift_hw = -1; p.slab = nullptr; p.bslab = nullptr; p.slab_stride = 0;
-    p.dy = dy; p.x = x; p.dw = dw; p.dbias = dbias;
-    p.N = N; p.Hin = H; p.Win = W; p.Cin = Cin; p.Cout = Cout;
-    p.Hout = (H + 2 * pad - ks) / stride + 1;
-    p.Wout = (W + 2 * pad - ks) / stride + 1;
-    p.stride = stride; p.pad = pad; p.Kdim = ks * ks * Cin; p.M = N * p.Hout * p.Wout;
-    p.cshift = ks == 1 ? 0 : ilog2_exact(Cin);
-    p.x_bytes = (unsigned)((size_t)N * H * W * Cin * es); p.dy_bytes = (unsigned)((size_t)p.M * Cout * es);
+    const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
+    WgP p = make_wgrad_params(dy, x, dw, N, H, W, Cin, Ho, Wo, Cout, ks, stride, pad, act_f32);
+    p.dbias = dbias;
     if (!accumulate) {
         const int64_t nz = (int64_t)Cout * p.Kdim;
         hipLaunchKernelGGL(k_fill_zero_f32, dim3((unsigned)cr_cdiv(nz, 256)), dim3(256), 0, ctx->stream, dw, nz);
         CR_LAUNCH_CHECK();
     }
-    if (act_f32 == 2 && ks == 3) {
-        int rcr = CR_OK;
-        if (try_launch_wgrad_s3_row(ctx, p, &rcr)) return rcr;
-    }
-    if (act_f32 == 2 && ks != 7) {
-        int rc3 = CR_OK;
-        if (ks == 1 ? try_launch_wgrad_s3<1>(ctx, p, &rc3) : try_launch_wgrad_s3<3>(ctx, p, &rc3)) return rc3;
-    }
-    if (act_f32 && ks != 1) {
-        int rcp = CR_OK;
-        if (try_launch_wgrad_patch_f32(ctx, p, ks, &rcp)) return rcp;
-    }
+    if (act_f32 == 2 && ks == 3 && (rc = try_launch_wgrad_s3_row(ctx, p)) != NOT_TAKEN) return rc;
+    if (act_f32 == 2 && ks != 7 &&
+        (rc = ks == 1 ? try_launch_wgrad_s3<1>(ctx, p) : try_launch_wgrad_s3<3>(ctx, p)) != NOT_TAKEN)
+        return rc;
+    if (act_f32 && ks != 1 && (rc = try_launch_wgrad_patch_f32(ctx, p, ks)) != NOT_TAKEN) return rc;
     if (act_f32) {
         if (ks == 1) return launch_wgrad_f32_ks<1>(ctx, p);
         if (ks == 3) return launch_wgrad_f32_ks<3>(ctx, p);
@@ -3102,12 +3023,7 @@ extern "C" int cr_wgrad_batched_f32(cr_ctx* ctx, const float* dy, const float* x
                                     int64_t stride_dy, int64_t stride_x, int64_t stride_dw) {
     CR_CHECK_ARG(ctx && dy && x && dw && R > 0 && batches >= 1 && batches <= 65535, "cr_wgrad_batched_f32: bad args");
     CR_CHECK_ARG(O % 128 == 0 && K % 32 == 0, "cr_wgrad_batched_f32: O %% 128 == 0, K %% 32 == 0");
-    WgP p;
-    p.dbg = 0; p.cshift_w = 0; p.cshift_hw = -1; p.slab = nullptr; p.bslab = nullptr; p.slab_stride = 0;
-    p.dy = dy; p.x = x; p.dw = dw; p.dbias = nullptr;
-    p.N = 1; p.Hin = 1; p.Win = R; p.Cin = K; p.Cout = O; p.Hout = 1; p.Wout = R;
-    p.stride = 1; p.pad = 0; p.Kdim = K; p.M = R; p.cshift = 0;
-    p.x_bytes = (unsigned)((size_t)R * K * 4); p.dy_bytes = (unsigned)((size_t)R * O * 4);
+    WgP p = make_wgrad_params(dy, x, dw, 1, 1, R, K, 1, R, O, 1, 1, 0, 1);    // a 1 x R image of K channels, 1x1 filter
     const int nsteps = (R + 15) / 16;
     const int tm = O / 128, tn = (int)cr_cdiv(K, 128);
     const int tiles = tm * tn * batches;
@@ -3118,7 +3034,7 @@ extern "C" int cr_wgrad_batched_f32(cr_ctx* ctx, const float* dy, const float* x
     p.steps_per_split = (nsteps + splits - 1) / splits;
     p.steps_per_split = (p.steps_per_split + 1) & ~1;
     splits = (nsteps + p.steps_per_split - 1) / p.steps_per_split;
-    p.tm = tm; p.tn = tn; p.xcd = xcd_enabled();
+    p.tm = tm; p.tn = tn;
     const int count = tm * tn * splits;
     const int64_t n = (int64_t)batches * stride_dw;
     if (deterministic_on() && ctx->ws && stride_dw == (int64_t)O * K && (size_t)splits * n * sizeof(float) <= ctx->ws_bytes) {
@@ -3157,17 +3073,13 @@ extern "C" int cr_conv2d_bwd_weight_group(cr_ctx* ctx, int n, const void* const*
         CR_CHECK_ARG(dys[i] && xs[i] && dws[i], "cr_conv2d_bwd_weight_group: NULL tensor %d", i);
         int rc = conv_common_checks("cr_conv2d_bwd_weight_group", Ns[i], Hs[i], Ws[i], Cin, Cout, ks, 1, pad, act_f32);
         if (rc) return rc;
+        const int H = Hs[i], W = Ws[i], Ho = H + 2 * pad - ks + 1, Wo = W + 2 * pad - ks + 1;
         WgP& p = g.p[i];
-        p.dbg = 0; p.cshift_w = 0; p.cshift_hw = -1; p.slab = nullptr; p.bslab = nullptr; p.slab_stride = 0;
-        p.dy = dys[i]; p.x = xs[i]; p.dw = dws[i]; p.dbias = dbiases ? dbiases[i] : nullptr;
-        p.N = Ns[i]; p.Hin = Hs[i]; p.Win = Ws[i]; p.Cin = Cin; p.Cout = Cout;
-        p.Hout = Hs[i] + 2 * pad - ks + 1; p.Wout = Ws[i] + 2 * pad - ks + 1;
-        p.stride = 1; p.pad = pad; p.Kdim = ks * ks * Cin; p.M = p.N * p.Hout * p.Wout;
-        p.cshift = ks == 1 ? 0 : ilog2_exact(Cin);
-        p.x_bytes = (unsigned)((size_t)p.N * p.Hin * p.Win * Cin * 4); p.dy_bytes = (unsigned)((size_t)p.M * Cout * 4);
+        p = make_wgrad_params(dys[i], xs[i], dws[i], Ns[i], H, W, Cin, Ho, Wo, Cout, ks, 1, pad, act_f32);
+        p.dbias = dbiases ? dbiases[i] : nullptr;
         const int nsteps = (p.M + PS - 1) / PS;
         p.steps_per_split = sps;
-        p.tm = tm; p.tn = tn; p.xcd = xcd_enabled();
+        p.tm = tm; p.tn = tn;
         counts[i] = tiles * (int)cr_cdiv(nsteps, sps);
     }
     // deterministic mode: every problem gets its own slabs (all of them, or none: shared parameters must not mix the two forms)
@@ -3558,17 +3470,15 @@ __global__ __launch_bounds__(256) void k_bn_apply_fused(const T* __restrict__ x,
     }
 }
 
-static int bn_fuse_rows() {
-    static const int v = env_int("CR_BN_FUSE_ROWS", 256);
-    return v;
-}
+// at most this many statistics rows take the fused finalize + apply (k_bn_apply_fused): the 64x64 and smaller maps
+static constexpr int BN_FUSE_ROWS = 256;
 
 extern "C" int cr_bn_fwd(cr_ctx* ctx, const void* x, const float* stats, int nparts, const float* gamma,
                          const float* beta, const void* residual, void* y, int64_t M, int C, int relu, float eps,
                          float momentum, float* mean_invstd, float* running_mean, float* running_var, int act_f32) {
     CR_CHECK_ARG(ctx && x && stats && gamma && beta && y && mean_invstd, "cr_bn_fwd: NULL pointer");
     CR_CHECK_ARG(M > 0 && C > 0 && C % 8 == 0 && nparts > 0, "cr_bn_fwd: bad dims M=%lld C=%d", (long long)M, C);
-    if (C % 32 == 0 && nparts <= bn_fuse_rows()) {
+    if (C % 32 == 0 && nparts <= BN_FUSE_ROWS) {
         // ~1024 blocks; a block's statistics pass reads nparts x 64 floats
         int64_t chunks = 1024 / (C / 32);
         if (chunks < 1) chunks = 1;
@@ -3779,7 +3689,7 @@ extern "C" int cr_bn_bwd(cr_ctx* ctx, const void* dy, const void* out, const voi
         hipLaunchKernelGGL(k_bn_bwd_reduce<u16>, dim3((unsigned)nb), dim3(256), shm, ctx->stream, (const u16*)dy,
                            (const u16*)out, (const u16*)x, mean_invstd, sums, M, C, relu);
     CR_LAUNCH_CHECK();
-    if (C % 32 == 0 && nb <= bn_fuse_rows()) {
+    if (C % 32 == 0 && nb <= BN_FUSE_ROWS) {
         int64_t chunks = 1024 / (C / 32);
         if (chunks < 1) chunks = 1;
         int64_t ppb = cr_cdiv(M, chunks);

@@ -9,7 +9,6 @@
 //   nms / batched_nms                              cubercnn/modeling/roi_heads/fast_rcnn.py:105; detectron2 RPN
 #include "cr_common.h"
 #include <math.h>
-#include <stdlib.h>
 
 #include "cr_elem.h"
 
@@ -619,15 +618,14 @@ extern "C" int cr_roi_align_bwd(cr_ctx* ctx, float* const* grads, const int* Hs,
     Pyramid py;
     int rc = fill_pyramid(py, nullptr, grads, Hs, Ws, scales, nlev, C);
     if (rc) return rc;
-    if (PH == 7 && PW == 7 && !getenv("CR_ROI_BWD_PLAIN")) {
+    if (PH == 7 && PW == 7) {
         int maxH = 0, maxW = 0;
         for (int l = 0; l < nlev; ++l) { maxH = Hs[l] > maxH ? Hs[l] : maxH; maxW = Ws[l] > maxW ? Ws[l] : maxW; }
         const size_t lds = (size_t)(maxH + maxW) * 7 * sizeof(float);
         if (lds <= 60 * 1024) {
-            static const int xg_on = getenv("CR_ROI_BWD_XCD") ? atoi(getenv("CR_ROI_BWD_XCD")) : 1;
-            static const int xg_threads = getenv("CR_ROI_BWD_T") ? atoi(getenv("CR_ROI_BWD_T")) : 128;   // 4 row phases x 32 channels
-            if (xg_on && C % 256 == 0 && R * 8 < 0x7fffffff) {       // C / 8 channels per block, a multiple of a 128-B line
-                const int nt = (C / 8) * (xg_threads / (C / 8) > 0 ? xg_threads / (C / 8) : 1);
+            constexpr int XG_THREADS = 128;                          // 4 row phases x 32 channels
+            if (C % 256 == 0 && R * 8 < 0x7fffffff) {               // C / 8 channels per block, a multiple of a 128-B line
+                const int nt = (C / 8) * (XG_THREADS / (C / 8) > 0 ? XG_THREADS / (C / 8) : 1);
                 if (act_f32)
                     hipLaunchKernelGGL((k_roi_align_bwd_sep<7, float, 8>), dim3((unsigned)R * 8), dim3(nt), lds, ctx->stream, py,
                                        rois, (int)R, (const float*)dout, maxH);

@@ -955,8 +955,7 @@ extern "C" int cr_mask_rects(cr_ctx* ctx, const unsigned char* masks, const unsi
     hipLaunchKernelGGL(k_mask_bbox, dim3((unsigned)cr_cdiv(H, 32), (unsigned)n), block, 0, ctx->stream, src, H, W, bbox);
     // the run-based kernel first (LDS only; 13 ints of LDS per row); what it leaves goes through the pixel-label passes
     const size_t run_lds = sizeof(int) * (size_t)H * (3 * RUN_MAXR + 1);
-    static const bool runs_on = []() { const char* e = getenv("CR_MASK_RUNS"); return !(e && e[0] == '0'); }();
-    if (runs_on && run_lds <= 64 * 1024 && W < 32768)
+    if (run_lds <= 64 * 1024 && W < 32768)
         hipLaunchKernelGGL(k_mask_rect_runs, dim3((unsigned)n), dim3(RECT_T), run_lds, ctx->stream, src, H, W, bbox, rects, valid);
     hipLaunchKernelGGL(k_ccl_init, grid, block, 0, ctx->stream, src, H, W, (const int*)bbox, labels, sizes);
     hipLaunchKernelGGL(k_ccl_merge, grid, block, 0, ctx->stream, H, W, (const int*)bbox, labels);

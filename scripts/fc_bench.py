@@ -1,5 +1,5 @@
 """Times the RoI heads' FC layers (box head fc1 2048 x 12544 -> 1024, cube head fc1 on ~512 foreground rows, fc2 1024 -> 1024)
-in the three directions; environment switches (CR_SPLITK_TARGET, CR_CONV_BM64, CR_WG_F32_TM ...) are read by the library."""
+in the three directions, on the routes the library picks for these shapes."""
 import importlib, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ops = importlib.import_module("3dod_amd.hipops")

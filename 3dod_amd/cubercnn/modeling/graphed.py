@@ -35,6 +35,18 @@ def capture_guard():
         _empty_graveyard()
 
 
+def dense_bn_modules(model):
+    """the BatchNorm2d layers of the captured dense region (trunk + FPN + RPN head)"""
+    return [m for mod in (model.backbone, model.proposal_generator.rpn_head) for m in mod.modules()
+            if isinstance(m, nn.BatchNorm2d)]
+
+
+def bn_mode(bns):
+    """which of these BatchNorm layers run in training mode: a region captured with train-mode statistics (batch statistics,
+    running-statistics updates) and one captured after freeze_bn (folded running statistics) are different graphs"""
+    return tuple(m.training for m in bns)
+
+
 _GRAVEYARD = []      # state of graph owners whose destructor ran while a capture was open; emptied outside captures
 
 
@@ -133,6 +145,8 @@ class GraphedDense(GraphOwner):
         self.model = model
         self.shape = tuple(images_u8.shape)
         self.dtype = ops.precision()        # the captured kernels are those of this precision mode
+        self._bns = dense_bn_modules(model)
+        self.bn_mode = bn_mode(self._bns)   # ... and of these BatchNorm modes (freeze_bn)
         dev = self.dev = images_u8.device
         self.static_img = images_u8.clone()
         self.pre_bwd = None                 # optional callback run right before the backward graph is replayed
@@ -213,7 +227,8 @@ class GraphedDense(GraphOwner):
                     ops.grad_sink(p).add_(g)
 
         # the warm-up and capture passes below run the BatchNorm layers in training mode: their running statistics are
-        # put back afterwards, so capturing a shape in the middle of a run (RCNN3D._train_graph_for) leaves no trace
+        # put back afterwards, so capturing a shape in the middle of a run (RCNN3D._train_graph_for) leaves no trace (frozen
+        # BatchNorm layers never write them)
         bn_state = [(m, m.running_mean.clone(), m.running_var.clone(), m.num_batches_tracked.clone())
                     for mod in mods for m in mod.modules()
                     if isinstance(m, nn.BatchNorm2d) and m.running_mean is not None]
@@ -256,12 +271,12 @@ class GraphedDense(GraphOwner):
         self._bank_param = next((p for mod in mods for p in mod.parameters() if hasattr(p, "_cr_bank")), None)
 
     def matches(self, images_u8):
-        """same batch shape, device and precision mode, and the weight bank the graphs were captured against is still the
-        one attached to the parameters (a bank rebuilt by the optimizer means new compute-copy buffers)"""
+        """same batch shape, device, precision mode and BatchNorm modes, and the weight bank the graphs were captured against
+        is still the one attached to the parameters (a bank rebuilt by the optimizer means new compute-copy buffers)"""
         bp = self._bank_param
         bank_now = getattr(bp, "_cr_bank", (None,))[0] if bp is not None else None
         return (tuple(images_u8.shape) == self.shape and images_u8.device == self.static_img.device
-                and ops.precision() == self.dtype and bank_now is self.bank)
+                and ops.precision() == self.dtype and bank_now is self.bank and bn_mode(self._bns) == self.bn_mode)
 
     def __call__(self, images_u8):
         self.static_img.copy_(images_u8)

@@ -68,7 +68,7 @@ class RCNN3D(nn.Module):
             il, batch = self._stack_images(sample_batched_inputs)
             self._graphed = GraphedDense(self, batch, split_backward=split_backward)
             if self._graphed_max > 0:
-                self._graphed_cache[(self._graphed.shape, ops.precision())] = self._graphed
+                self._graphed_cache[(self._graphed.shape, ops.precision(), self._graphed.bn_mode)] = self._graphed
         return self._graphed
 
     def disable_graphs(self):
@@ -84,7 +84,8 @@ class RCNN3D(nn.Module):
         cache = self._graphed_cache
         if not self._graphed_max or cache is None:
             return None
-        key = (tuple(batch.shape), ops.precision())
+        from ..graphed import bn_mode, dense_bn_modules
+        key = (tuple(batch.shape), ops.precision(), bn_mode(dense_bn_modules(self)))     # freeze_bn: a graph of its own
         g = cache.get(key)
         if g is not None and not g.matches(batch):            # e.g. the optimizer's weight bank was rebuilt: capture again
             del cache[key]

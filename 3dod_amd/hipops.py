@@ -403,12 +403,11 @@ class _ConvBN(torch.autograd.Function):
         ctx.slots = slots
         _p = _Args()
         Cout, Cin, k, _ = weight.shape
-        need_grad = x.requires_grad or weight.requires_grad
-        wb, wt = prepared_weights(weight, need_grad and x.requires_grad, x.dtype)
         dev = x.device
         af = _af(x)
         lib = _lib.load()
         if training:
+            wb, _ = prepared_weights(weight, x.requires_grad, x.dtype)
             _STATS_EPOCH[0] += 1
             N_, H_, W_, _ = x.shape
             M = N_ * ((H_ + 2 * pad - k) // stride + 1) * ((W_ + 2 * pad - k) // stride + 1)
@@ -421,16 +420,24 @@ class _ConvBN(torch.autograd.Function):
                                _p(out), M, Cout, int(relu), float(eps), float(momentum), _p(mi), _p(running_mean),
                                _p(running_var), af), "cr_bn_fwd")
         else:
-            # frozen statistics with gradients enabled (freeze_bn fine-tuning; plain inference takes conv_bn_folded): an
-            # affine epilogue (scale*x + shift) done by the BN kernel with mean/invstd taken from the running buffers
-            y_raw = conv_fwd_raw(x, wb, Cout, k, stride, pad)
-            M = y_raw.numel() // Cout
-            mi = torch.stack([running_mean, torch.rsqrt(running_var + eps)]).contiguous()
-            out = torch.empty_like(y_raw)
-            # one "partial" that reproduces (mean, var): sum = mean*M, sumsq = (var+mean^2)*M
-            zstats = torch.stack([running_mean * M, (running_var + running_mean * running_mean) * M]).view(1, 2, Cout).contiguous()
-            _chk(lib.cr_bn_fwd(_ctx(x), _p(y_raw), _p(zstats), 1, _p(gamma.detach()), _p(beta.detach()), _p(residual),
-                               _p(out), M, Cout, int(relu), float(eps), 0.0, _p(mi), _p(None), _p(None), af), "cr_bn_fwd")
+            # frozen statistics with gradients enabled (freeze_bn fine-tuning; plain inference takes conv_bn_folded): the
+            # BatchNorm folded into the convolution (cr_fold_bn) and ONE convolution with bias / residual / ReLU in its
+            # epilogue.  The fold is made on every call from the live parameters -- inside a graph capture it is a node of
+            # the graph -- and never shares the inference fold cache (weight._cr_fold*).  The f32 folded weight is kept for
+            # the backward (its transposed copy for backward-data); y_raw is never written.
+            K_ = weight.numel() // Cout
+            wf32 = torch.empty((Cout, K_), dtype=f32, device=dev)
+            bias_f = torch.empty((Cout,), dtype=f32, device=dev)
+            _chk(lib.cr_fold_bn(_ctx(x), _p(weight.detach()), _p(gamma.detach()), _p(beta.detach()), _p(running_mean),
+                                _p(running_var), float(eps), _p(wf32), _p(bias_f), Cout, K_, 1), "cr_fold_bn")
+            if x.dtype == bf16:
+                wf = torch.empty((Cout, K_), dtype=bf16, device=dev)
+                _chk(lib.cr_cast_f32_to_bf16(_ctx(x), _p(wf32), _p(wf), wf32.numel()), "cr_cast_f32_to_bf16")
+            else:
+                wf = wf32
+            out = conv_fwd_raw(x, wf, Cout, k, stride, pad, bias=bias_f, residual=residual, relu=relu)
+            y_raw, mi = wf32, None
+            ctx.frozen = (running_mean, running_var, float(eps))
         ctx.cfg = (k, stride, pad, relu, training, residual is not None)
         ctx.beta_ref = beta
         ctx.save_for_backward(x, weight, gamma, y_raw, out if relu else None, mi)
@@ -451,7 +458,7 @@ class _ConvBN(torch.autograd.Function):
         need_dx = ctx.needs_input_grad[0] if want_dx is None else want_dx
         need_dw = ctx.needs_input_grad[1] if want_dw is None else want_dw
         if not training:
-            raise _lib.CrError("backward through frozen BatchNorm is not implemented")
+            return _ConvBN._frozen_backward(ctx, dout, need_dx, need_dw, root)
         Cout = weight.shape[0]
         dev = x.device
         dout = dout.to(x.dtype).contiguous()
@@ -488,6 +495,64 @@ class _ConvBN(torch.autograd.Function):
             return dx_raw, dw, ret_g, ret_b
         return dx, dw, ret_g, ret_b, dres, None, None, None, None, None, None, None, None, None
 
+    @staticmethod
+    def _frozen_backward(ctx, dout, need_dx, need_dw, root):
+        """backward of the folded forward: g = dout masked by the ReLU (= the residual's gradient), dx = conv_bwd_data(g, wf^T),
+        dwf = conv_bwd_weight(g, x) and sum_p g into scratch in one launch, then cr_bn_frozen_unfold maps them to dw, dgamma
+        and dbeta (into the parameters' gradient sinks when they have them).  root: _RootConvBN forms the children's
+        gradients itself from g and ctx.frozen_wt."""
+        _p = _Args()
+        x, weight, gamma, wf32, out, _ = ctx.saved_tensors
+        k, stride, pad, relu, _, has_res = ctx.cfg
+        running_mean, running_var, eps = ctx.frozen
+        Cout, Cin = weight.shape[0], weight.shape[1]
+        K_ = weight.numel() // Cout
+        dev = x.device
+        lib = _lib.load()
+        dout = dout.to(x.dtype).contiguous()
+        g = relu_bwd(out, dout) if relu else dout
+        (xslot, xi), (rslot, ri) = ctx.slots
+        dres = g if has_res else None
+        if rslot is not None and dres is not None:          # the residual's other consumer (a convolution) adds this
+            _slot_put(rslot, dres)
+            dres = None
+        dx = None
+        if need_dx or root:
+            wt = torch.empty((Cin, k * k * Cout), dtype=x.dtype, device=dev)        # [Cin][k*k][Cout]
+            assert wt.numel() == wf32.numel()
+            _chk(lib.cr_weight_transpose(_ctx(x), _p(wf32), _p(wt), Cout, k, Cin, int(x.dtype == f32)), "cr_weight_transpose")
+            if root:
+                ctx.frozen_wt = wt
+            elif xslot is not None and xi > 1:              # not the first consumer of x: leave the contribution in the slot
+                _slot_put(xslot, conv_bwd_data_raw(g, wt, x.shape, k, stride, pad, accumulate=_slot_fold(xslot)))
+            else:
+                acc = _slot_take(xslot) if xslot is not None else None
+                dx = conv_bwd_data_raw(g, wt, x.shape, k, stride, pad, accumulate=acc)
+        elif xslot is not None:
+            raise RuntimeError("gradient slot registered for an input that needs no gradient")
+        # dgamma needs <dwf, w> even when the weight itself needs no gradient; sum_p g rides on the weight-gradient launch
+        sg = torch.zeros((Cout,), dtype=f32, device=dev)
+        dwf = conv_bwd_weight_raw(g, x, k, stride, pad, None, bias_acc=sg)
+        wsink = grad_sink(weight) if need_dw else None
+        dw = None
+        if need_dw and wsink is None:
+            dw = dwf                                        # scaled in place
+        gs, bs = grad_sink(gamma), grad_sink(ctx.beta_ref)
+        if gs is not None and bs is not None:
+            dgamma, dbeta, ret_g, ret_b = gs, bs, None, None
+        else:
+            dgamma = torch.zeros((Cout,), dtype=f32, device=dev)
+            dbeta = torch.zeros((Cout,), dtype=f32, device=dev)
+            ret_g, ret_b = dgamma, dbeta
+        dst = wsink if wsink is not None else dw
+        assert dwf.numel() == Cout * K_ and (dst is None or dst.numel() == Cout * K_) and dgamma.numel() == Cout == dbeta.numel()
+        _chk(lib.cr_bn_frozen_unfold(_ctx(x), _p(dwf), _p(sg), _p(weight.detach()), _p(gamma.detach()), _p(running_mean),
+                                     _p(running_var), eps, _p(dst), int(wsink is not None), _p(dgamma), _p(dbeta), Cout, K_),
+             "cr_bn_frozen_unfold")
+        if root:
+            return g, dw, ret_g, ret_b
+        return dx, dw, ret_g, ret_b, dres, None, None, None, None, None, None, None, None, None
+
 
 class _RootConvBN(torch.autograd.Function):
     """DLA `Root` (dla.py:156-174): 1x1 convolution + BatchNorm (+ ReLU) over the channel concatenation of its children.
@@ -497,10 +562,10 @@ class _RootConvBN(torch.autograd.Function):
     consumed first gets its share through that convolution's gradient slot instead of an autograd add."""
 
     @staticmethod
-    def forward(ctx, weight, gamma, beta, running_mean, running_var, relu, eps, momentum, slots, *children):
+    def forward(ctx, weight, gamma, beta, running_mean, running_var, relu, eps, momentum, training, slots, *children):
         with torch.no_grad():
             x = torch.cat(children, 3)
-        out = _ConvBN.forward(ctx, x, weight, gamma, beta, None, running_mean, running_var, 1, 0, relu, eps, momentum, True)
+        out = _ConvBN.forward(ctx, x, weight, gamma, beta, None, running_mean, running_var, 1, 0, relu, eps, momentum, training)
         ctx.child_slots = slots
         ctx.child_ch = [c.shape[3] for c in children]
         return out
@@ -514,12 +579,12 @@ class _RootConvBN(torch.autograd.Function):
         ctx.slots = ((None, 0), (None, 0))
         res = _ConvBN._backward_impl(ctx, dout, want_dx=False, want_dw=need[0])
         dx_raw, dw, ret_g, ret_b = res
-        _, wt = prepared_weights(weight, True, x.dtype)
+        wt = ctx.frozen_wt if hasattr(ctx, "frozen_wt") else prepared_weights(weight, True, x.dtype)[1]
         outs, c0 = [], 0
         N, H, W, _ = x.shape
         for i, ci in enumerate(ctx.child_ch):
             g = None
-            if need[9 + i]:
+            if need[10 + i]:
                 slot, idx = ctx.child_slots[i]
                 g = conv_bwd_data_raw(dx_raw, wt[c0:c0 + ci], (N, H, W, ci), 1, 1, 0,
                                       accumulate=_slot_fold(slot) if slot is not None else None)
@@ -530,18 +595,22 @@ class _RootConvBN(torch.autograd.Function):
                 raise RuntimeError("gradient slot registered for an input that needs no gradient")
             outs.append(g)
             c0 += ci
-        return (dw, ret_g, ret_b, None, None, None, None, None, None) + tuple(outs)
+        return (dw, ret_g, ret_b, None, None, None, None, None, None, None) + tuple(outs)
 
 
 def root_conv_bn_act(children, weight, gamma, beta, running_mean, running_var, relu=True, eps=1e-5, momentum=0.1, training=True):
-    """conv_bn_act(torch.cat(children, 3), 1x1 weight, ...) for DLA's Root nodes in training mode (see _RootConvBN)"""
+    """conv_bn_act(torch.cat(children, 3), 1x1 weight, ...) for DLA's Root nodes with gradients (see _RootConvBN); training:
+    the BatchNorm's mode (False: frozen statistics, freeze_bn)"""
     children = list(children)
-    if not (training and torch.is_grad_enabled() and _ROOT_FUSED[0] and all(c.dim() == 4 for c in children)
+    grad = torch.is_grad_enabled() and (training or weight.requires_grad or gamma.requires_grad or beta.requires_grad
+                                        or any(c.requires_grad for c in children))
+    if not (grad and _ROOT_FUSED[0] and all(c.dim() == 4 for c in children)
             and all(c.shape[3] % 16 == 0 for c in children) and weight.shape[2] == 1):
         return conv_bn_act(torch.cat(children, 3), weight, gamma, beta, running_mean, running_var, 1, 0, relu, None, eps,
                            momentum, training)
     slots = tuple(_slot_register(c, False) for c in children)
-    return _RootConvBN.apply(as_krsc(weight), gamma, beta, running_mean, running_var, relu, eps, momentum, slots, *children)
+    return _RootConvBN.apply(as_krsc(weight), gamma, beta, running_mean, running_var, relu, eps, momentum, bool(training), slots,
+                             *children)
 
 
 _ROOT_FUSED = [os.environ.get("CR_ROOT_FUSED", "1") == "1"]

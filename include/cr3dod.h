@@ -360,6 +360,16 @@ int cr_bn_fwd(cr_ctx* ctx, const void* x, const float* stats, int nparts, const 
 int cr_bn_bwd(cr_ctx* ctx, const void* dy, const void* out, const void* x, const float* mean_invstd,
               const float* gamma, float* sums, void* dx, void* dres, float* dgamma, float* dbeta, int64_t M,
               int C, int relu, int act_f32);
+/* BatchNorm2d in eval mode with trainable gamma / beta (freeze_bn fine-tuning), backward after the folded forward
+ * (cr_fold_bn + cr_conv2d_fwd with bias, residual, ReLU): from dwf (Cout, K) f32 = weight gradient of the folded convolution
+ * (cr_conv2d_bwd_weight_bias on g = dout masked by the ReLU) and sg (Cout) = its fused bias gradient, per channel c with
+ * s = gamma * rsqrt(var + eps):  dw[c] = s * dwf[c] (accumulate = 0) or += (1); dbeta[c] += sg[c];
+ * dgamma[c] += rsqrt(var + eps) * (dot(dwf[c], w[c]) - mean[c] * sg[c]).  w / dw (Cout, K) f32 in the kernels'
+ * [Cout][kh][kw][Cin] order; dw may be NULL (no weight gradient) or equal dwf when accumulate = 0.  One workgroup per
+ * channel, fixed-order reduction, no atomics. */
+int cr_bn_frozen_unfold(cr_ctx* ctx, const float* dwf, const float* sg, const float* w, const float* gamma,
+                        const float* mean, const float* var, float eps, float* dw, int accumulate, float* dgamma,
+                        float* dbeta, int Cout, int K);
 
 /* window 2: MaxPool2d(2,2) (dla.py:208); window 1: max_pool2d(k=1,s=2) (dla.py:474). */
 int cr_pool2x_fwd(cr_ctx* ctx, const void* x, void* y, int N, int H, int W, int C, int window, int act_f32);

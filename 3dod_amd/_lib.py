@@ -99,6 +99,10 @@ SIGNATURES = {
     "cr_cube_select_bwd": [P, P, c_int, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P],
     "cr_cube_reduce": [P, P, P, P, P, c_int, c_int, P, P, P],
     "cr_cube_reduce_bwd": [P, P, P, P, c_int, c_int, P, P, P, P],
+    "cr_cube_select_norm": [P, P, c_int, P, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P],
+    "cr_cube_nondis_fwd": [P, P, P, c_int64, c_int, c_int, c_int, c_int, P, P],
+    "cr_cube_nondis_bwd": [P, P, P, c_int64, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P],
+    "cr_cube_select_bwd_zraw": [P, c_int, P, c_int, c_int, c_int, P, P, P, P, c_int, P, P],
     "cr_weights_prepare": [P, P, P, P, P, P, c_int, c_int],
     "cr_fc_weight_prepare": [P, P, P, c_int, c_int, c_int, c_int],
     "cr_fc_grad_accum": [P, P, P, c_int, c_int, c_int, c_int],

@@ -477,6 +477,264 @@ extern "C" int cr_cube_select_bwd(cr_ctx* ctx, const float* raw, int ld, const i
     return CR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// MODEL.ROI_CUBE_HEAD.DISENTANGLED_LOSS False (roi_heads.py:2516-2560, joint term :2582-2591): every quantity is compared in
+// its own normalised space instead of through cuboid corners.  Same interface as k_cube_loss<>: one lane per RoI, losses (n,5) =
+// [dims, xy, z, pose, joint] x sqrt(2) exp(-u), dec (n,17), the five gradient arrays.  Per RoI:
+//   xy     mean_2 |delta - (gt2d - box centre) / (box w, h)|                                             (:2525-2528)
+//   dims   mean_3 |raw - log(gt dims)|, raw = before the clip at 5; no dimension priors                  (:2536)
+//   pose   1 - (trace(P T^T) - 1) / 2; allocentric: P = R_alloc, T = M^T gtR with M the ray rotation through the predicted
+//          centre (detached, angle > 0 rule of ray_rotation); else P = R, T = gtR          (:2540-2544, math_util.py:746-774)
+//   z      direct |z v2r - gtz| ; sigmoid |sigmoid(raw) - clip(gtz r2v / 100, 0, 1)| ; log |raw - log(max(gtz r2v, 0.01))| ;
+//          clusters |raw - (gtz r2v - mean) / std| ; r2v = 1 / v2r                                        (:2550-2560)
+//   joint  mean_24 |corners(predicted cuboid) - corners(gt)|, never chamfer                               (:2587-2591)
+// The pre-decode depth and the cluster statistics come in `norm` (3, n) = [raw depth | mean | std] (cr_cube_select_norm): they
+// are not recovered from the decoded depth, whose derivative underflows for a saturated sigmoid.  The z term of sigmoid / log /
+// clusters differentiates to the RAW depth: g_zraw (n); g_zr keeps d / d(decoded depth) (joint term, direct z term).
+// ---------------------------------------------------------------------------------------------------------------
+struct NondisCommon {
+    float cux, cuy, z, dims[3], R[9], T[9], M[9], sf, L[5], pa, pb, sw, sh, sz, sxy[2], sd[3];
+    bool rot;
+};
+
+// forward of every term but the joint one; sz / sxy / sd = signs of the residuals
+__device__ __forceinline__ void nondis_terms(const CubeIn& in, const float* __restrict__ norm, int z_type, int i, NondisCommon& c) {
+    const float* sb = in.src_boxes + i * 4;
+    const float* K4 = in.K4 + i * 4;
+    c.sw = sb[2] - sb[0]; c.sh = sb[3] - sb[1];
+    const float ctx = sb[0] + 0.5f * c.sw, cty = sb[1] + 0.5f * c.sh;
+    const float dx = in.dxy[i * 2], dy = in.dxy[i * 2 + 1];
+    c.cux = ctx + c.sw * dx; c.cuy = cty + c.sh * dy;
+    const float rx = dx - (in.gt2d[i * 2] - ctx) / c.sw, ry = dy - (in.gt2d[i * 2 + 1] - cty) / c.sh;
+    c.sxy[0] = sgn(rx); c.sxy[1] = sgn(ry);
+    c.L[1] = (fabsf(rx) + fabsf(ry)) * 0.5f;
+    float ld = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float r = in.dr[i * 3 + k];
+        c.dims[k] = expf(fminf(r, 5.0f)) * in.prior_mean[i * 3 + k];
+        const float d = r - logf(in.gtdims[i * 3 + k]);
+        c.sd[k] = sgn(d);
+        ld += fabsf(d);
+    }
+    c.L[0] = ld / 3.f;
+    c.rot = false;
+    if (in.allocentric) c.rot = ray_rotation(c.cux, c.cuy, K4, c.M);
+    const float* Ra = in.Ra + i * 9;
+    const float* gR = in.gtR + i * 9;
+    float tr = 0.f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            c.R[a * 3 + b] = c.rot ? (c.M[a * 3] * Ra[b] + c.M[a * 3 + 1] * Ra[3 + b]) + c.M[a * 3 + 2] * Ra[6 + b] : Ra[a * 3 + b];
+            // T = M^T gtR: the ground truth in the allocentric frame of the predicted ray
+            c.T[a * 3 + b] = c.rot ? (c.M[a] * gR[b] + c.M[3 + a] * gR[3 + b]) + c.M[6 + a] * gR[6 + b] : gR[a * 3 + b];
+            tr += Ra[a * 3 + b] * c.T[a * 3 + b];
+        }
+    c.L[3] = 1.f - (tr - 1.f) * 0.5f;
+    const float v2r = in.v2r[i], gz = in.gtz[i];
+    c.z = in.zr[i] * v2r;
+    const float gv = gz * (1.f / v2r);
+    float rz;
+    if (z_type == 1) rz = 1.f / (1.f + expf(-norm[i])) - fminf(fmaxf(gv / 100.f, 0.f), 1.f);
+    else if (z_type == 2) rz = norm[i] - logf(fmaxf(gv, 0.01f));
+    else if (z_type == 3) rz = norm[i] - (gv - norm[in.n + i]) / norm[2 * in.n + i];
+    else rz = c.z - gz;
+    c.sz = sgn(rz);
+    c.L[2] = fabsf(rz);
+    c.sf = in.use_conf ? SQRT2F * expf(-in.u[i]) : 1.0f;
+    c.pa = (c.cux - K4[2]) / K4[0]; c.pb = (c.cuy - K4[3]) / K4[1];
+}
+
+__device__ __forceinline__ void nondis_gt_corners(const CubeIn& in, int i, float G[8][3]) {
+    const float* K4 = in.K4 + i * 4;
+    const float gz = in.gtz[i];
+    const float gc[3] = {gz * ((in.gt2d[i * 2] - K4[2]) / K4[0]), gz * ((in.gt2d[i * 2 + 1] - K4[3]) / K4[1]), gz};
+    corners(gc, in.gtdims + i * 3, in.gtR + i * 9, G);
+}
+
+__global__ __launch_bounds__(CH_T) void k_cube_nondis_fwd(CubeIn in, const float* __restrict__ norm, int z_type,
+                                                          float* __restrict__ losses, float* __restrict__ dec) {
+    const int i = blockIdx.x * CH_T + threadIdx.x;
+    if (i >= in.n) return;
+    NondisCommon c;
+    nondis_terms(in, norm, z_type, i, c);
+    c.L[4] = 0.f;
+    if (in.joint) {
+        float G[8][3], P[8][3];
+        nondis_gt_corners(in, i, G);
+        const float c_j[3] = {c.z * c.pa, c.z * c.pb, c.z};
+        corners(c_j, c.dims, c.R, P);
+        c.L[4] = l1_corner(P, G, nullptr, 0.f, false);
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) losses[i * 5 + k] = c.L[k] * c.sf;
+    float* o = dec + i * 17;
+    o[0] = c.cux; o[1] = c.cuy; o[2] = c.z; o[3] = c.dims[0]; o[4] = c.dims[1]; o[5] = c.dims[2];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) o[6 + k] = c.R[k];
+    o[15] = c.z * c.pa; o[16] = c.z * c.pb;
+}
+
+__global__ __launch_bounds__(CH_T) void k_cube_nondis_bwd(CubeIn in, const float* __restrict__ norm, int z_type,
+                                                          const float* __restrict__ gl, float* __restrict__ g_dxy,
+                                                          float* __restrict__ g_zr, float* __restrict__ g_dr,
+                                                          float* __restrict__ g_Ra, float* __restrict__ g_u,
+                                                          float* __restrict__ g_zraw) {
+    const int i = blockIdx.x * CH_T + threadIdx.x;
+    if (i >= in.n) return;
+    NondisCommon c;
+    nondis_terms(in, norm, z_type, i, c);
+    const float* K4 = in.K4 + i * 4;
+    float up[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) up[k] = gl[i * 5 + k] * c.sf;
+    float d_cux = 0.f, d_cuy = 0.f, d_z = 0.f, d_dims[3] = {0, 0, 0}, d_R[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    c.L[4] = 0.f;
+    if (in.joint) {
+        float G[8][3], P[8][3], dP[8][3];
+        nondis_gt_corners(in, i, G);
+        const float c_j[3] = {c.z * c.pa, c.z * c.pb, c.z};
+        corners(c_j, c.dims, c.R, P);
+        c.L[4] = l1_corner(P, G, dP, up[4], true);
+        float dc[3] = {0, 0, 0};
+        corners_bwd(dP, c.dims, c.R, dc, d_dims, nullptr);
+        // dR[a][b] = sum_v dP[v][a] loc_v[b], one scalar accumulator per entry
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                float s = 0.f;
+#pragma unroll
+                for (int v = 0; v < 8; ++v) {
+                    float l[3];
+                    loc_of(v, c.dims, l);
+                    s += dP[v][a] * l[b];
+                }
+                d_R[a * 3 + b] = s;
+            }
+        d_z += (dc[0] * c.pa + dc[1] * c.pb) + dc[2];
+        d_cux += dc[0] * c.z / K4[0];
+        d_cuy += dc[1] * c.z / K4[1];
+    }
+    // the xy term acts on the raw deltas, the dims term on the raw dimensions (also above the clip at 5)
+    g_dxy[i * 2] = d_cux * c.sw + c.sxy[0] * up[1] * 0.5f;
+    g_dxy[i * 2 + 1] = d_cuy * c.sh + c.sxy[1] * up[1] * 0.5f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const bool clip = !(in.dr[i * 3 + k] <= 5.0f);
+        g_dr[i * 3 + k] = (clip ? 0.f : d_dims[k] * c.dims[k]) + c.sd[k] * up[0] / 3.f;
+    }
+    float zraw = 0.f;
+    if (z_type == 0) d_z += c.sz * up[2];
+    else if (z_type == 1) { const float sg = 1.f / (1.f + expf(-norm[i])); zraw = (c.sz * up[2]) * (sg * (1.f - sg)); }
+    else zraw = c.sz * up[2];
+    g_zr[i] = d_z * in.v2r[i];
+    g_zraw[i] = zraw;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {        // joint: dRa = M^T dR; pose: d(1 - (tr - 1) / 2) / dRa = -T / 2
+            const float j = c.rot ? (c.M[a] * d_R[b] + c.M[3 + a] * d_R[3 + b]) + c.M[6 + a] * d_R[6 + b] : d_R[a * 3 + b];
+            g_Ra[i * 9 + a * 3 + b] = j - 0.5f * up[3] * c.T[a * 3 + b];
+        }
+    float du = 0.f;
+    if (in.use_conf) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) du -= gl[i * 5 + k] * (c.L[k] * c.sf);
+    }
+    g_u[i] = du;
+}
+
+// norm (3, n) = [raw depth of the RoI's (bin, class) column | cluster mean | cluster std] (0 / 1 unless Z_TYPE 'clusters')
+__global__ __launch_bounds__(64) void k_cube_select_norm(CubeSel p, const int* __restrict__ clsc, float* __restrict__ norm) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= p.n) return;
+    const int c = clsc[i];
+    const int bin = z_bin(p.z_scales, p.boxes, p.bins, i, c);
+    norm[i] = p.raw[(size_t)i * p.ld + p.o_z + bin * p.K + c];
+    norm[p.n + i] = p.z_type == 3 ? p.z_stats[(c * p.bins + bin) * 2] : 0.f;
+    norm[2 * p.n + i] = p.z_type == 3 ? p.z_stats[(c * p.bins + bin) * 2 + 1] : 1.f;
+}
+
+// g_raw[i][depth column of RoI i] += g_zraw[i] on the valid RoIs, after cr_cube_select_bwd wrote the dense gradient
+__global__ __launch_bounds__(64) void k_cube_select_bwd_zraw(CubeSel p, const unsigned char* __restrict__ validf,
+                                                             const int* __restrict__ clsc, const float* __restrict__ g_zraw,
+                                                             float* __restrict__ g_raw) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= p.n || !validf[i]) return;
+    const int c = clsc[i];
+    g_raw[(size_t)i * p.ld + p.o_z + z_bin(p.z_scales, p.boxes, p.bins, i, c) * p.K + c] += g_zraw[i];
+}
+
+static int cube_norm_args(CubeSel& p, const float* raw, int ld, const int* layout5, int K, int B, int kf, int z_type, int bins,
+                          const float* z_scales, const float* z_stats, const float* boxes) {
+    CR_CHECK_ARG(raw && layout5 && B > 0 && kf > 0 && K > 0 && bins >= 1 && ld >= (12 + bins) * K, "cube_select_norm: bad sizes");
+    CR_CHECK_ARG(z_type >= 0 && z_type <= 3 && (bins == 1 || (z_scales && boxes)) && (z_type != 3 || (bins > 1 && z_stats)),
+                 "cube_select_norm: z_type %d / bins %d", z_type, bins);
+    p = CubeSel{};
+    p.raw = raw; p.ld = ld; p.o_z = layout5[3]; p.K = K; p.kf = kf; p.n = B * kf;
+    p.z_type = z_type; p.bins = bins; p.z_scales = z_scales; p.z_stats = z_stats; p.boxes = boxes;
+    return CR_OK;
+}
+
+extern "C" int cr_cube_select_norm(cr_ctx* ctx, const float* raw, int ld, const int* layout5, int K, int B, int kf,
+                                   const int* clsc, int z_type, int bins, const float* z_scales, const float* z_stats,
+                                   const float* boxes, float* norm3) {
+    CR_CHECK_ARG(ctx && clsc && norm3, "cr_cube_select_norm: NULL pointer");
+    CubeSel p;
+    int rc = cube_norm_args(p, raw, ld, layout5, K, B, kf, z_type, bins, z_scales, z_stats, boxes);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_cube_select_norm, dim3((unsigned)cr_cdiv(p.n, 64)), dim3(64), 0, ctx->stream, p, clsc, norm3);
+    CR_LAUNCH_CHECK();
+    return CR_OK;
+}
+
+extern "C" int cr_cube_select_bwd_zraw(cr_ctx* ctx, int ld, const int* layout5, int K, int B, int kf,
+                                       const unsigned char* validf, const int* clsc, const float* g_zraw, float* g_raw,
+                                       int bins, const float* z_scales, const float* boxes) {
+    CR_CHECK_ARG(ctx && validf && clsc && g_zraw && g_raw, "cr_cube_select_bwd_zraw: NULL pointer");
+    CubeSel p;
+    int rc = cube_norm_args(p, g_raw, ld, layout5, K, B, kf, 0, bins, z_scales, nullptr, boxes);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_cube_select_bwd_zraw, dim3((unsigned)cr_cdiv(p.n, 64)), dim3(64), 0, ctx->stream, p, validf, clsc,
+                       g_zraw, g_raw);
+    CR_LAUNCH_CHECK();
+    return CR_OK;
+}
+
+// inputs: HOST array of 13 device pointers in the order of CubeIn; norm3 from cr_cube_select_norm.  losses (n,5), dec (n,17).
+extern "C" int cr_cube_nondis_fwd(cr_ctx* ctx, const float* const* inputs, const float* norm3, int64_t n, int allocentric,
+                                  int use_conf, int joint, int z_type, float* losses, float* dec) {
+    CR_CHECK_ARG(ctx && inputs && n >= 0 && z_type >= 0 && z_type <= 3, "cr_cube_nondis_fwd: bad args");
+    if (n == 0) return CR_OK;
+    CR_CHECK_ARG(norm3 && losses && dec, "cr_cube_nondis_fwd: NULL pointer");
+    CubeIn in;
+    int rc = cube_args(in, inputs, n, allocentric, 0, use_conf, joint);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_cube_nondis_fwd, dim3((unsigned)cr_cdiv(n, CH_T)), dim3(CH_T), 0, ctx->stream, in, norm3, z_type,
+                       losses, dec);
+    CR_LAUNCH_CHECK();
+    return CR_OK;
+}
+
+// gl (n,5) = d(total)/d(losses); outputs g_dxy (n,2) g_zr (n) g_dr (n,3) g_Ra (n,9) g_u (n) g_zraw (n)
+extern "C" int cr_cube_nondis_bwd(cr_ctx* ctx, const float* const* inputs, const float* norm3, int64_t n, int allocentric,
+                                  int use_conf, int joint, int z_type, const float* gl, float* g_dxy, float* g_zr,
+                                  float* g_dr, float* g_Ra, float* g_u, float* g_zraw) {
+    CR_CHECK_ARG(ctx && inputs && n >= 0 && z_type >= 0 && z_type <= 3, "cr_cube_nondis_bwd: bad args");
+    if (n == 0) return CR_OK;
+    CR_CHECK_ARG(norm3 && gl && g_dxy && g_zr && g_dr && g_Ra && g_u && g_zraw, "cr_cube_nondis_bwd: NULL pointer");
+    CubeIn in;
+    int rc = cube_args(in, inputs, n, allocentric, 0, use_conf, joint);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_cube_nondis_bwd, dim3((unsigned)cr_cdiv(n, CH_T)), dim3(CH_T), 0, ctx->stream, in, norm3, z_type, gl,
+                       g_dxy, g_zr, g_dr, g_Ra, g_u, g_zraw);
+    CR_LAUNCH_CHECK();
+    return CR_OK;
+}
+
 // red (6) = mean over the valid, finite entries of [dims, xy, z, pose, joint] (x inverse-z weight) and of the uncertainty
 // (0 when there is none); cnt (6); stats (4) = mean |z|, |dims|, |xy| errors and mean exp(-u) over the valid RoIs.
 __global__ __launch_bounds__(256) void k_cube_reduce(const float* __restrict__ L, const float* __restrict__ buf,

@@ -324,10 +324,13 @@ def cube_head_losses(rh, features, samp, pred_boxes, gt: GTBatch, meta, pooled=N
     raw, layout = rh.cube_head.forward_fused(cube_features)
     assert rh.use_confidence > 0 and rh.dims_priors_func == "exp"
     priors = rh.priors_dims_per_cat.detach()[0, :, 0, :].contiguous() if rh.dims_priors_enabled else None
+    # DISENTANGLED_LOSS False is passed only when set: the CPU stand-in of this op (oracle/cpu_backend.py) states the default
+    # family and has no such argument, so it raises instead of computing the wrong loss
+    family = {} if rh.disentangled_loss else {"disentangled": False}
     L, u_sel, dec, buf, validf = ops.cube_head_loss(raw, layout, K, samp["classes"], samp["valid"], samp["gt_idx"], kf,
                                                     gt.boxes3D, gt.poses, priors, meta, boxes.reshape(n, 4),
                                                     allocentric=rh.allocentric_pose, chamfer_pose=rh.chamfer_pose,
-                                                    use_conf=True, joint=rh.loss_w_joint > 0, z_cfg=rh.z_cfg())
+                                                    use_conf=True, joint=rh.loss_w_joint > 0, z_cfg=rh.z_cfg(), **family)
     red, stats = ops.cube_reduce(L, u_sel, buf, dec, validf, inverse_z=bool(rh.inverse_z_weight))
     p = "Cube/"
     w3 = rh.loss_w_3d

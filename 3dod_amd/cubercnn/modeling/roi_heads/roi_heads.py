@@ -162,9 +162,12 @@ class ROIHeads3D(StandardROIHeads):
         self.cluster_bins = c.CLUSTER_BINS
         self.dims_priors_enabled = c.DIMS_PRIORS_ENABLED
         self.dims_priors_func = c.DIMS_PRIORS_FUNC
-        if self.z_type not in ('direct', 'sigmoid', 'log', 'clusters') or not self.disentangled_loss:
-            raise ValueError("built: Z_TYPE 'direct' / 'sigmoid' / 'log' / 'clusters' with the disentangled loss (configs/Base.yaml); "
-                             "got Z_TYPE '{}', DISENTANGLED_LOSS {}".format(self.z_type, self.disentangled_loss))
+        if self.z_type not in ('direct', 'sigmoid', 'log', 'clusters'):
+            raise ValueError("built: Z_TYPE 'direct' / 'sigmoid' / 'log' / 'clusters'; got Z_TYPE '{}'".format(self.z_type))
+        if not self.disentangled_loss and self.dims_priors_enabled:
+            # roi_heads.py:2532 divides gt_dims (n,3) by the stacked prior mean / std (n,2,3): a broadcasting error for n > 2
+            raise ValueError("DISENTANGLED_LOSS False is built with DIMS_PRIORS_ENABLED False only: with DIMS_PRIORS_ENABLED True "
+                             "the reference itself fails (roi_heads.py:2532), so there is nothing to reproduce")
         if self.z_type == 'clusters' and self.cluster_bins <= 1:
             raise ValueError('To use z_type of priors, there must be more than 1 cluster bin')       # roi_heads.py:2044
         if self.loss_w_3d > 0 and (self.use_confidence <= 0 or (self.dims_priors_enabled and self.dims_priors_func != 'exp')):
@@ -394,6 +397,9 @@ class ROIHeads3D(StandardROIHeads):
                 raise RuntimeError("ROIHeads3D._forward_cube on instance lists in training mode / on CPU tensors: the product "
                                    "trains on the static-shape path (model.dense_train = True) and has no CPU path; the list "
                                    "formulation is oracle/cube_list.py")
+            if self.training and not self.disentangled_loss:
+                raise RuntimeError("the list formulation (oracle/cube_list.py) states the disentangled losses only; "
+                                   "DISENTANGLED_LOSS False trains on the static-shape path (dense_train.cube_head_losses)")
             return listed(features, instances, Ks, im_current_dims, im_scales_ratio)
         boxes = [x.pred_boxes for x in instances]
         if sum(len(b) for b in boxes) == 0:

@@ -2053,10 +2053,87 @@ class _CubeHeadLoss(torch.autograd.Function):
         return (g_raw.to(dt),) + (None,) * 12
 
 
+class _CubeHeadLossNondis(torch.autograd.Function):
+    """_CubeHeadLoss with the non-disentangled losses (MODEL.ROI_CUBE_HEAD.DISENTANGLED_LOSS False, roi_heads.py:2516-2560): the
+    same select / reduce kernels around cr_cube_nondis_fwd / _bwd; three rows after the 39 of `buf` carry the pre-decode depth and
+    the cluster statistics, and the z term's gradient w.r.t. the raw depth is added to the depth column by its own launch."""
+
+    @staticmethod
+    def forward(ctx, raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, meta, boxes, flags):
+        _p = _Args()
+        _need_cuda(raw, "cube head output")
+        B, S = cls.shape
+        n = B * kf
+        dev = raw.device
+        raw32 = raw.detach().float().contiguous()
+        buf42 = torch.empty((42 * n,), dtype=f32, device=dev)
+        buf, norm = buf42[:39 * n], buf42[39 * n:]
+        validf = torch.empty((n,), dtype=torch.uint8, device=dev)
+        clsc = torch.empty((n,), dtype=torch.int32, device=dev)
+        lay = (_ct.c_int * 5)(*[int(v) for v in layout])
+        lib = _lib.load()
+        boxes = boxes.float().contiguous()
+        zc = flags[3]
+        _chk(lib.cr_cube_select(_ctx(raw), _p(raw32), raw32.shape[1], lay, int(K), _p(cls.contiguous()),
+                                _p(valid.to(torch.uint8).contiguous()), _p(gt_idx.contiguous()), B, S, int(kf), gt3d.shape[1],
+                                _p(gt3d.contiguous()), _p(gtpose.contiguous()), _p(None), _p(meta.contiguous()), _p(buf),
+                                _p(validf), _p(clsc), zc[0], zc[1], _p(zc[2]), _p(zc[3]), _p(boxes)), "cr_cube_select")
+        _chk(lib.cr_cube_select_norm(_ctx(raw), _p(raw32), raw32.shape[1], lay, int(K), B, int(kf), _p(clsc), zc[0], zc[1],
+                                     _p(zc[2]), _p(zc[3]), _p(boxes), _p(norm)), "cr_cube_select_norm")
+        ch = _chunks(buf, n)
+        ins = ch[:5] + [boxes] + ch[5:]
+        arr = (ctypes.c_void_p * 13)(*[t.data_ptr() for t in ins])
+        losses = torch.empty((n, 5), dtype=f32, device=dev)
+        dec = torch.empty((n, 17), dtype=f32, device=dev)
+        _chk(lib.cr_cube_nondis_fwd(_ctx(raw), ctypes.cast(arr, ctypes.c_void_p), _p(norm), n, *flags[:3], zc[0], _p(losses),
+                                    _p(dec)), "cr_cube_nondis_fwd")
+        ctx.keep = (raw32, buf42, validf, clsc, boxes, tuple(layout), int(K), B, int(kf), flags, raw.dtype)
+        ctx.set_materialize_grads(False)       # outputs nobody differentiates arrive as None, not as zero fills
+        ctx.mark_non_differentiable(dec, buf, validf)
+        return losses, ch[4].clone(), dec, buf, validf
+
+    @staticmethod
+    def backward(ctx, gl, g_usel, _gd, _gb, _gv):
+        _p = _Args()
+        raw32, buf42, validf, clsc, boxes, layout, K, B, kf, flags, dt = ctx.keep
+        n = B * kf
+        dev = raw32.device
+        buf, norm = buf42[:39 * n], buf42[39 * n:]
+        ch = _chunks(buf, n)
+        ins = ch[:5] + [boxes] + ch[5:]
+        arr = (ctypes.c_void_p * 13)(*[t.data_ptr() for t in ins])
+        g = torch.empty((17 * n,), dtype=f32, device=dev)
+        g_dxy, g_zr, g_dr, g_Ra, g_u, g_zraw = g[:2 * n], g[2 * n:3 * n], g[3 * n:6 * n], g[6 * n:15 * n], g[15 * n:16 * n], g[16 * n:]
+        lib = _lib.load()
+        zc = flags[3]
+        _chk(lib.cr_cube_nondis_bwd(_ctx(raw32), ctypes.cast(arr, ctypes.c_void_p), _p(norm), n, *flags[:3], zc[0],
+                                    _p(gl.contiguous()), _p(g_dxy), _p(g_zr), _p(g_dr), _p(g_Ra), _p(g_u), _p(g_zraw)),
+             "cr_cube_nondis_bwd")
+        g_raw = torch.empty_like(raw32)
+        lay = (_ct.c_int * 5)(*layout)
+        _chk(lib.cr_cube_select_bwd(_ctx(raw32), _p(raw32), raw32.shape[1], lay, K, B, kf, _p(validf), _p(clsc), _p(g_dxy),
+                                    _p(g_zr), _p(g_dr), _p(g_Ra), _p(g_u), _p(g_usel.contiguous()), _p(g_raw), zc[0], zc[1],
+                                    _p(zc[2]), _p(zc[3]), _p(boxes)), "cr_cube_select_bwd")
+        if zc[0] != 0:                         # 'direct' has no normalised depth space: its z term went through g_zr
+            _chk(lib.cr_cube_select_bwd_zraw(_ctx(raw32), raw32.shape[1], lay, K, B, kf, _p(validf), _p(clsc), _p(g_zraw),
+                                             _p(g_raw), zc[1], _p(zc[2]), _p(boxes)), "cr_cube_select_bwd_zraw")
+        return (g_raw.to(dt),) + (None,) * 11
+
+
 def cube_head_loss(raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors, meta, boxes, allocentric=True,
-                   chamfer_pose=True, use_conf=True, joint=True, z_type="direct", z_cfg=None):
+                   chamfer_pose=True, use_conf=True, joint=True, z_type="direct", z_cfg=None, disentangled=True):
     """raw (n,13K) fused predictor output; cls/valid/gt_idx (B,S); gt3d (B,G,9); gtpose (B,G,3,3); priors (K,3) or None;
-    meta (B,5); boxes (n,4).  -> losses (n,5), u_sel (n), dec (n,17), buf39, validf (n) uint8."""
+    meta (B,5); boxes (n,4).  -> losses (n,5), u_sel (n), dec (n,17), buf39, validf (n) uint8.
+    disentangled=False: the non-disentangled losses of MODEL.ROI_CUBE_HEAD.DISENTANGLED_LOSS False (roi_heads.py:2516-2560);
+    `priors` must be None (the reference fails with the dimension priors there, :2532) and `chamfer_pose` plays no part (the
+    pose term is the relative rotation angle, the joint term is L1, :2587-2591)."""
+    if not disentangled:
+        if priors is not None:
+            raise ValueError("cube_head_loss: the non-disentangled loss is built without dimension priors "
+                             "(DIMS_PRIORS_ENABLED False): the reference fails with them (roi_heads.py:2532)")
+        flags = (int(bool(allocentric)), int(bool(use_conf)), int(bool(joint)), z_cfg or z_config(z_type))
+        return _CubeHeadLossNondis.apply(raw, tuple(layout), K, cls, valid, gt_idx, kf, gt3d,
+                                         gtpose.reshape(gtpose.shape[0], -1, 9), meta, boxes, flags)
     flags = (int(bool(allocentric)), int(bool(chamfer_pose)), int(bool(use_conf)), int(bool(joint)), z_cfg or z_config(z_type))
     return _CubeHeadLoss.apply(raw, tuple(layout), K, cls, valid, gt_idx, kf, gt3d, gtpose.reshape(gtpose.shape[0], -1, 9),
                                priors, meta, boxes, flags)

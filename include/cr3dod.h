@@ -539,6 +539,31 @@ int cr_cube_reduce(cr_ctx* ctx, const float* L, const float* buf39, const float*
 int cr_cube_reduce_bwd(cr_ctx* ctx, const float* L, const float* buf39, const unsigned char* validf, int n, int inverse_z,
                        const float* cnt6, const float* gred6, float* gL, float* gu);
 
+/* ---- MODEL.ROI_CUBE_HEAD.DISENTANGLED_LOSS False: the non-disentangled losses of the 3D head (roi_heads.py:2516-2560, joint
+ * term :2582-2591), additive to the entries above; cr_cube_select / _select_bwd / _reduce / _reduce_bwd are used as they are.
+ * Per RoI, columns [dims, xy, z, pose, joint] x sqrt(2) exp(-u) like cr_cube_loss_fwd:
+ *   xy mean_2 |delta - (gt2d - box centre) / (box w, h)| (:2525-2528); dims mean_3 |raw - log(gt dims)|, raw = before the clip at
+ *   5, no dimension priors (:2536); pose 1 - (trace(P T^T) - 1) / 2 with P = the head's (allocentric) matrix and T = the ground
+ *   truth taken to the allocentric frame of the ray through the predicted centre (:2540-2544, math_util.py:746-774); z in the space
+ *   of z_type: 0 |z v2r - gtz|, 1 |sigmoid(raw) - clip(gtz r2v / 100, 0, 1)|, 2 |raw - log(max(gtz r2v, 0.01))|, 3 |raw - (gtz r2v -
+ *   mean) / std|, r2v = 1 / v2r (:2550-2560); joint mean-L1 over the 24 corner coordinates, never chamfer (:2587-2591).
+ * cr_cube_select_norm: norm3 (3*n f32) = [raw depth of the RoI's (bin, class) column | cluster mean | cluster std] (0 / 1 unless
+ * z_type 3), clsc from cr_cube_select: what the z term needs and the decoded depth of buf39 cannot give back. */
+int cr_cube_select_norm(cr_ctx* ctx, const float* raw, int ld, const int* layout5, int K, int B, int kf, const int* clsc,
+                        int z_type, int bins, const float* z_scales, const float* z_stats, const float* boxes, float* norm3);
+/* inputs: HOST array of the 13 device pointers of cr_cube_loss_fwd.  losses (n,5), dec (n,17) as there. */
+int cr_cube_nondis_fwd(cr_ctx* ctx, const float* const* inputs, const float* norm3, int64_t n, int allocentric, int use_conf,
+                       int joint, int z_type, float* losses, float* dec);
+/* gradients like cr_cube_loss_bwd; g_zr = d / d(decoded depth) (joint term, z term of z_type 0), g_zraw (n) = d / d(raw depth) of
+ * the z term of z_type 1..3, which cr_cube_select_bwd_zraw adds to the depth column after cr_cube_select_bwd (:2404-2436). */
+int cr_cube_nondis_bwd(cr_ctx* ctx, const float* const* inputs, const float* norm3, int64_t n, int allocentric, int use_conf,
+                       int joint, int z_type, const float* gl, float* g_dxy, float* g_zr, float* g_dr, float* g_Ra, float* g_u,
+                       float* g_zraw);
+/* g_raw[i][depth column of RoI i] += g_zraw[i] on the valid RoIs (the column choice of roi_heads.py:2343-2356). */
+int cr_cube_select_bwd_zraw(cr_ctx* ctx, int ld, const int* layout5, int K, int B, int kf, const unsigned char* validf,
+                            const int* clsc, const float* g_zraw, float* g_raw, int bins, const float* z_scales,
+                            const float* boxes);
+
 /* ---- test-time filter of the box head on padded proposals, without a host round trip -----------------------------------
  * FastRCNNOutputs.inference -> fast_rcnn_inference_single_image (cubercnn/modeling/roi_heads/fast_rcnn.py:57-116): softmax,
  * score threshold, Box2BoxTransform.apply_deltas + Boxes.clip, class-wise NMS (torchvision batched_nms), the best `topk`

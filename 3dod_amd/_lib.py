@@ -4,6 +4,8 @@ import ctypes
 import os
 import threading
 
+import torch    # (also: torch's libamdhip64 has to be in the process before libcr3dod.so pulls in a HIP runtime, see load())
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libcr3dod.so")
 
@@ -145,8 +147,7 @@ def load():
                 f"{LIB_PATH} not found: build it with `python 3dod_amd/build.py` "
                 "(or __graft_entry__.build()). There is no fallback path.")
         # torch ships its own libamdhip64; it has to be in the process BEFORE this library pulls in a HIP runtime, or
-        # two runtimes coexist and the second one sees no device ("no ROCm-capable device is detected")
-        import torch  # noqa: F401
+        # two runtimes coexist and the second one sees no device ("no ROCm-capable device is detected"): imported above
         lib = ctypes.CDLL(LIB_PATH)
         lib.cr_last_error.restype = ctypes.c_char_p
         lib.cr_last_error.argtypes = []
@@ -164,6 +165,11 @@ def check(rc, what):
         raise CrError(f"{what} failed (rc={rc}): {msg}")
 
 
+def topk_blocks(n, k):
+    """cr_topk_blocks: a host-side count, no context and no status"""
+    return load().cr_topk_blocks(n, k)
+
+
 # ---- per-device context bound to torch's current stream ---------------------
 _ctxs = {}
 
@@ -171,12 +177,11 @@ _ctxs = {}
 def ctx_for(device):
     """cr_ctx for a torch cuda device, re-pointed at torch's CURRENT stream on
     every call so library launches order with surrounding torch work."""
-    import torch
     lib = load()
     if device.type != "cuda":
         raise CrError(f"3dod_amd kernels run on the GPU only (got device '{device}'); there is no CPU path")
     idx = device.index if device.index is not None else torch.cuda.current_device()
-    stream = torch.cuda.current_stream(idx).cuda_stream
+    stream = torch._C._cuda_getCurrentRawStream(idx)    # = torch.cuda.current_stream(idx).cuda_stream without the Stream object (1 us)
     ctx = _ctxs.get(idx)
     if ctx is None:
         h = P()
@@ -192,7 +197,38 @@ def ptr(t):
     if t is None:
         return P(None)
     if not t.is_contiguous():
-        import torch
         if not (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)):
             raise CrError("tensor must be dense (contiguous or channels_last)")
     return P(t.data_ptr())
+
+
+_NULL, _Tensor = P(None), torch.Tensor
+
+
+def call(name, *args, device=None):
+    """lib.<name>(ctx, *args) with the status checked: the one way kernels are launched from Python.  `args` is the header's
+    argument list without the leading cr_ctx*.  Tensors are passed as their device pointers (ptr()), None as NULL, everything
+    else unchanged (ints, floats, ctypes arrays / casts).  The context is that of `device`, or of the first tensor argument
+    (`device=` is for calls whose arguments are host pointer tables only).
+
+    `args` references every tensor until the C function has returned -- i.e. until the launch has been enqueued on the
+    stream -- so a temporary may be written inline: call("cr_x", x.float().contiguous(), ...).  After that the caching
+    allocator's stream ordering (eager) or the capture's allocation order (HIP graphs) makes reuse of the block safe.  A
+    temporary that dies as soon as its pointer has been read can hand its block to the NEXT temporary of the same argument
+    list before the kernel is even launched (round 1: garbage sampling indices -> out-of-bounds gathers in cr_roi_compact,
+    the memory fault of the whole-step graph mode)."""
+    if name not in SIGNATURES:
+        raise CrError(f"{name} is not an entry point of libcr3dod.so (see SIGNATURES)")
+    fn = getattr(load(), name)
+    conv = []
+    for a in args:
+        if a is None:
+            a = _NULL
+        elif type(a) is not int and isinstance(a, _Tensor):       # (most arguments are ints; Tensor's isinstance is a slow one)
+            if device is None:
+                device = a.device
+            a = ptr(a)
+        conv.append(a)
+    if device is None:
+        raise CrError(f"{name}: no tensor argument and no device= to take the context from")
+    check(fn(ctx_for(device), *conv), name)

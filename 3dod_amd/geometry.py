@@ -26,9 +26,7 @@ def cuboid_corners(box6, R):
     n = box6.shape[0]
     R = _f32c(R, "R", (n, 3, 3))
     verts = torch.empty((n, 8, 3), dtype=f32, device=box6.device)
-    lib = _lib.load()
-    _lib.check(lib.cr_cuboid_corners(_lib.ctx_for(box6.device), _lib.ptr(box6), _lib.ptr(R), n, _lib.ptr(verts)),
-               "cr_cuboid_corners")
+    _lib.call("cr_cuboid_corners", box6, R, n, verts)
     return verts
 
 
@@ -75,20 +73,14 @@ def cubes_project_score(cubes, K, im_wh, ref_boxes, prior_mu, prior_sigma, rect_
         out["best"] = torch.empty((N,), dtype=f32, device=dev)
     if N == 0:
         return out
-    lib = _lib.load()
     extra = ()
     if fast:
         if stats is not None and (stats.dtype != torch.int64 or stats.numel() != 2 or not stats.is_cuda):
             raise ValueError("stats must be an int64 device tensor of 2 elements")
-        extra = (_lib.ptr(stats),)
-    fn = lib.cr_cubes_project_score_fast if fast else lib.cr_cubes_project_score
-    rc = fn(
-        _lib.ctx_for(dev), _lib.ptr(cubes), N, Pn, _lib.ptr(K), kpo, float(im_wh[0]), float(im_wh[1]),
-        _lib.ptr(ref_boxes), _lib.ptr(prior_mu), _lib.ptr(prior_sigma), _lib.ptr(rect_pts),
-        _lib.ptr(out["corners"]), _lib.ptr(out["boxes"]), _lib.ptr(out["iou"]), _lib.ptr(out["dim"]),
-        _lib.ptr(out["corner"]), _lib.ptr(out["combined"]), _lib.ptr(out["argmax"]), _lib.ptr(out["best"]),
-        _lib.ptr(iou_boxes), *extra)
-    _lib.check(rc, "cr_cubes_project_score")
+        extra = (stats,)
+    _lib.call("cr_cubes_project_score_fast" if fast else "cr_cubes_project_score", cubes, N, Pn, K, kpo, float(im_wh[0]),
+              float(im_wh[1]), ref_boxes, prior_mu, prior_sigma, rect_pts, out["corners"], out["boxes"], out["iou"], out["dim"],
+              out["corner"], out["combined"], out["argmax"], out["best"], iou_boxes, *extra)
     return out
 
 
@@ -111,12 +103,8 @@ def propose_from_draws(boxes, depth, prior_mu, prior_sigma, K, P, dim_normals, c
     normal = _f32c(normal, "normal", (3,))
     cubes = torch.empty((N, P, 15), dtype=f32, device=dev)
     exhausted = torch.zeros((1,), dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    rc = lib.cr_propose(_lib.ctx_for(dev), _lib.ptr(boxes), N, _lib.ptr(depth), H, W, _lib.ptr(prior_mu),
-                        _lib.ptr(prior_sigma), _lib.ptr(K), P, _lib.ptr(dim_normals), dim_normals.shape[0],
-                        _lib.ptr(ctr_normals), _lib.ptr(yaw_idx), _lib.ptr(normal), _lib.ptr(cubes),
-                        _lib.ptr(exhausted))
-    _lib.check(rc, "cr_propose")
+    _lib.call("cr_propose", boxes, N, depth, H, W, prior_mu, prior_sigma, K, P, dim_normals, dim_normals.shape[0], ctr_normals,
+              yaw_idx, normal, cubes, exhausted)
     return cubes, exhausted
 
 
@@ -138,11 +126,8 @@ def propose_from_draws_batched(boxes, img_idx, depth, prior_mu, prior_sigma, K, 
     assert tuple(yaw_idx.shape) == (N, P) and tuple(img_idx.shape) == (N,)
     cubes = torch.empty((N, P, 15), dtype=f32, device=dev)
     exhausted = torch.zeros((1,), dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    _lib.check(lib.cr_propose_batched(_lib.ctx_for(dev), _lib.ptr(boxes), _lib.ptr(img_idx), N, _lib.ptr(depth), B, H, W,
-                                      _lib.ptr(prior_mu), _lib.ptr(prior_sigma), _lib.ptr(K), P, _lib.ptr(dim_normals),
-                                      dim_normals.shape[0], _lib.ptr(ctr_normals), _lib.ptr(yaw_idx), _lib.ptr(normals),
-                                      _lib.ptr(cubes), _lib.ptr(exhausted)), "cr_propose_batched")
+    _lib.call("cr_propose_batched", boxes, img_idx, N, depth, B, H, W, prior_mu, prior_sigma, K, P, dim_normals,
+              dim_normals.shape[0], ctr_normals, yaw_idx, normals, cubes, exhausted)
     return cubes, exhausted
 
 
@@ -162,10 +147,7 @@ def ransac_plane_batched(pts, triples, eligible=None, thresh=0.05):
     neg_eq = torch.empty((B, 4), dtype=f32, device=dev)
     counts = torch.empty((B, T), dtype=torch.int32, device=dev)
     best = torch.empty((B, 2), dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    _lib.check(lib.cr_ransac_plane_batched(_lib.ctx_for(dev), _lib.ptr(pts), _lib.ptr(eligible), B, Q, _lib.ptr(triples), T,
-                                           float(thresh), _lib.ptr(neg_eq), _lib.ptr(counts), _lib.ptr(best)),
-               "cr_ransac_plane_batched")
+    _lib.call("cr_ransac_plane_batched", pts, eligible, B, Q, triples, T, float(thresh), neg_eq, counts, best)
     return neg_eq, counts, best
 
 
@@ -186,10 +168,7 @@ def ransac_plane(pts, triples, thresh=0.05, validate=True):
     neg_eq = torch.empty((4,), dtype=f32, device=dev)
     counts = torch.empty((T,), dtype=torch.int32, device=dev)
     best = torch.empty((2,), dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    rc = lib.cr_ransac_plane(_lib.ctx_for(dev), _lib.ptr(pts), Q, _lib.ptr(triples), T, float(thresh),
-                             _lib.ptr(neg_eq), _lib.ptr(counts), _lib.ptr(best))
-    _lib.check(rc, "cr_ransac_plane")
+    _lib.call("cr_ransac_plane", pts, Q, triples, T, float(thresh), neg_eq, counts, best)
     return neg_eq, counts, best
 
 
@@ -197,15 +176,13 @@ def box3d_overlap(boxes1, boxes2):
     """exact intersection volume and IoU of oriented 3D boxes: boxes1 (N,8,3), boxes2 (M,8,3) corners (pytorch3d order,
     as produced by get_cuboid_verts_faces) -> (vol (N,M), iou (N,M)).  Stands in for pytorch3d.ops.box3d_overlap at
     ProposalNetwork/utils/utils.py:207 and cubercnn/evaluation/omni3d_evaluation.py:155."""
-    lib = _lib.load()
     if not boxes1.is_cuda:
         raise _lib.CrError("box3d_overlap: expected CUDA(HIP) tensors; 3dod_amd has no CPU path")
     b1, b2 = boxes1.float().contiguous(), boxes2.float().contiguous()
     N, M = b1.shape[0], b2.shape[0]
     vol = torch.empty((N, M), dtype=torch.float32, device=b1.device)
     iou = torch.empty((N, M), dtype=torch.float32, device=b1.device)
-    _lib.check(lib.cr_box3d_overlap(_lib.ctx_for(b1.device), _lib.ptr(b1), _lib.ptr(b2), N, M, _lib.ptr(vol), _lib.ptr(iou)),
-               "cr_box3d_overlap")
+    _lib.call("cr_box3d_overlap", b1, b2, N, M, vol, iou)
     return vol, iou
 
 
@@ -213,22 +190,19 @@ def box_median(depth, boxes, img):
     """lower median (torch.median) of depth[img[i], y1:y2, x1:x2]: depth (B,H,W) f32, boxes (n,4) int32 (x1,y1,x2,y2),
     img (n) int32 -> (n,) f32, NaN for an empty window.  One radix-select block per box (cr_box_median) instead of the
     per-box loop of cubercnn/modeling/roi_heads/roi_heads.py:1216-1218."""
-    lib = _lib.load()
     if not depth.is_cuda:
         raise _lib.CrError("box_median: expected CUDA(HIP) tensors; 3dod_amd has no CPU path")
     d = depth.float().contiguous()
     assert d.dim() == 3 and boxes.dim() == 2 and boxes.shape[1] == 4 and img.shape[0] == boxes.shape[0]
     b, im = boxes.to(torch.int32).contiguous(), img.to(torch.int32).contiguous()
     out = torch.empty(b.shape[0], dtype=torch.float32, device=d.device)
-    _lib.check(lib.cr_box_median(_lib.ctx_for(d.device), _lib.ptr(d), d.shape[0], d.shape[1], d.shape[2], _lib.ptr(b),
-                                 _lib.ptr(im), b.shape[0], _lib.ptr(out)), "cr_box_median")
+    _lib.call("cr_box_median", d, d.shape[0], d.shape[1], d.shape[2], b, im, b.shape[0], out)
     return out
 
 
 def hull8(points):
     """convex hull of each RoI's 8 projected corners in the reference's order (cr_hull8): points (n,8,2) f32 ->
     order (n,8) int64, count (n) int32, bump (n,8) f32"""
-    lib = _lib.load()
     if not points.is_cuda:
         raise _lib.CrError("hull8: expected CUDA(HIP) tensors; 3dod_amd has no CPU path")
     p = points.detach().float().contiguous()
@@ -236,22 +210,20 @@ def hull8(points):
     order = torch.empty((n, 8), dtype=torch.int32, device=p.device)
     count = torch.empty((n,), dtype=torch.int32, device=p.device)
     bump = torch.empty((n, 8), dtype=torch.float32, device=p.device)
-    _lib.check(lib.cr_hull8(_lib.ctx_for(p.device), _lib.ptr(p), n, _lib.ptr(order), _lib.ptr(count), _lib.ptr(bump)), "cr_hull8")
+    _lib.call("cr_hull8", p, n, order, count, bump)
     return order.long(), count, bump
 
 
 class _PolygonFocal(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hull, count, masks, mask_idx):
-        lib = _lib.load()
         h = hull.detach().float().contiguous()
         n = h.shape[0]
         loss = torch.empty((n,), dtype=torch.float32, device=h.device)
         grad = torch.empty((n, 8, 2), dtype=torch.float32, device=h.device) if hull.requires_grad else None
         ones = (masks != 0).sum((1, 2)).to(torch.int32).contiguous()
-        _lib.check(lib.cr_polygon_focal(_lib.ctx_for(h.device), _lib.ptr(h), _lib.ptr(count), _lib.ptr(masks), _lib.ptr(mask_idx),
-                                        _lib.ptr(ones), n, masks.shape[1], masks.shape[2], _lib.ptr(loss),
-                                        _lib.ptr(grad) if grad is not None else None), "cr_polygon_focal")
+        _lib.call("cr_polygon_focal", h, count, masks, mask_idx, ones, n, masks.shape[1], masks.shape[2], loss,
+                  grad if grad is not None else None)
         ctx.grad = grad
         return loss
 
@@ -272,15 +244,13 @@ def polygon_focal(hull, count, masks, mask_idx):
 def segment_counts(corners2d, mask, stride=4):
     """per proposal: samples (stride*i, stride*j) inside the filled hull of its 8 projected corners, and how many of
     those the object mask covers (cr_segment_counts): corners2d (P,8,2) f32, mask (H,W) bool/uint8 -> (P,2) int64"""
-    lib = _lib.load()
     if not corners2d.is_cuda:
         raise _lib.CrError("segment_counts: expected CUDA(HIP) tensors; 3dod_amd has no CPU path")
     c = corners2d.detach().float().contiguous()
     m = mask.to(device=c.device, dtype=torch.uint8).contiguous()
     P = c.shape[0]
     out = torch.empty((P, 2), dtype=torch.int32, device=c.device)
-    _lib.check(lib.cr_segment_counts(_lib.ctx_for(c.device), _lib.ptr(c), P, _lib.ptr(m), m.shape[0], m.shape[1], int(stride),
-                                     _lib.ptr(out)), "cr_segment_counts")
+    _lib.call("cr_segment_counts", c, P, m, m.shape[0], m.shape[1], int(stride), out)
     return out.long()
 
 
@@ -305,7 +275,6 @@ def mask_rects(masks):
     score_corners, scorefunction.py:58-68): masks (n,H,W) bool/uint8 on the GPU, or a list of such tensors (the masks of
     several images: passed as a pointer table, not concatenated) -> rects (n,4,2) f32 (a NaN row for an empty mask),
     valid (n) bool"""
-    lib = _lib.load()
     many = isinstance(masks, (list, tuple))
     ms = [m for m in (masks if many else [masks])]
     if not all(m.is_cuda for m in ms):
@@ -328,6 +297,5 @@ def mask_rects(masks):
         import numpy as np
         table = torch.from_numpy(np.concatenate([m.data_ptr() + np.arange(m.shape[0], dtype=np.int64) * (H * W) for m in ms]))
         table = table.to(dev)
-    _lib.check(lib.cr_mask_rects(_lib.ctx_for(dev), _lib.ptr(dense), _lib.ptr(table), n, H, W, _lib.ptr(labels), _lib.ptr(sizes),
-                                 _lib.ptr(best), _lib.ptr(bbox), _lib.ptr(rects), _lib.ptr(valid)), "cr_mask_rects")
+    _lib.call("cr_mask_rects", dense, table, n, H, W, labels, sizes, best, bbox, rects, valid)
     return rects, valid.bool()

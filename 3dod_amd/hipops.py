@@ -73,47 +73,14 @@ def _w3(w, af):
         return None
     tag = (_WEIGHT_EPOCH[0], w.data_ptr(), w._version)
     if ent is None or ent[0] != tag:
-        _p = _Args()
         out = torch.empty((rows * K * 3,), dtype=bf16, device=w.device)
-        _chk(_lib.load().cr_weight_split3(_ctx(w), _p(w), _p(out), rows, K), "cr_weight_split3")
+        _lib.call("cr_weight_split3", w, out, rows, K)
         ent = (tag, out)
         try:
             w._cr_w3 = ent
         except Exception:
             pass
     return ent[1]
-
-
-def _ctx(t):
-    return _lib.ctx_for(t.device)
-
-
-def _chk(rc, what):
-    _lib.check(rc, what)
-
-
-class _Args:
-    """Owns the temporaries of ONE kernel call.  Every wrapper below starts with `_p = _Args()` and takes its device
-    pointers through it: `_p(x.contiguous())` may create a temporary, which this object keeps referenced until the wrapper
-    returns -- i.e. until the launch has been enqueued on the stream.  After that the caching allocator's stream ordering
-    (eager) or the capture's allocation order (HIP graphs) makes reuse of the block safe.  Without an owner a temporary dies
-    as soon as its pointer has been read and the NEXT temporary of the same argument list can be handed the same block
-    before the kernel is even launched (round 1: garbage sampling indices -> out-of-bounds gathers in cr_roi_compact, the
-    memory fault of the whole-step graph mode)."""
-    __slots__ = ("keep",)
-
-    def __init__(self):
-        self.keep = []
-
-    def __call__(self, t):
-        if t is not None:
-            self.keep.append(t)
-        return _lib.ptr(t)
-
-
-def _p(t):
-    """device pointer of a tensor the CALLER keeps alive across the launch (NULL for None)"""
-    return _lib.ptr(t)
 
 
 def _need_cuda(t, name):
@@ -217,14 +184,12 @@ class WeightBank:
             p._cr_bank = (self, i)
 
     def get(self, i):
-        _p = _Args()
         if self.epoch != _WEIGHT_EPOCH[0]:
-            lib = _lib.load()
-            _chk(lib.cr_weights_prepare(_ctx(self.flat_p), _p(self.flat_p), _p(self.dst), _p(self.dstT), _p(self.descs),
-                                        _p(self.tiles), self.ntiles, int(self.dtype == f32)), "cr_weights_prepare")
+            _lib.call("cr_weights_prepare", self.flat_p, self.dst, self.dstT, self.descs, self.tiles, self.ntiles,
+                      int(self.dtype == f32))
             if self.split:
                 for src, (descs, nd, tot) in zip((self.flat_p, self.dstT), self.s3):
-                    _chk(lib.cr_weights_split3(_ctx(self.flat_p), _p(src), _p(self.w3), _p(descs), nd, tot), "cr_weights_split3")
+                    _lib.call("cr_weights_split3", src, self.w3, descs, nd, tot)
             self.epoch = _WEIGHT_EPOCH[0]
         return self.views[i]
 
@@ -235,20 +200,17 @@ def prepared_weights(weight, need_transposed, dtype=bf16):
     same dtype come from the bank (one launch per step for the whole model); others are cached ON the tensor object (so
     a new tensor at a recycled address never hits a stale entry), keyed by torch's version counter and the global
     weight epoch."""
-    _p = _Args()
     bk = getattr(weight, "_cr_bank", None)
     if bk is not None and bk[0].dtype == dtype and (dtype == bf16 or bk[0].split or _ACT[0][1] != 2):
         return bk[0].get(bk[1])
     attr = "_cr_wcache" if dtype == bf16 else "_cr_wcache32"
     ent = getattr(weight, attr, None)
     tag = (weight._version, _WEIGHT_EPOCH[0], weight.data_ptr())
-    lib = _lib.load()
     if ent is None or ent[0] != tag:
         Cout, Cin, k, _ = weight.shape
         if dtype == bf16:
             wb = torch.empty((Cout, k * k * Cin), dtype=bf16, device=weight.device)
-            wd = weight.detach()
-            _chk(lib.cr_cast_f32_to_bf16(_ctx(weight), _p(wd), _p(wb), weight.numel()), "cr_cast_f32_to_bf16")
+            _lib.call("cr_cast_f32_to_bf16", weight.detach(), wb, weight.numel())
         else:
             wb = weight.detach()
         ent = [tag, wb, None]
@@ -259,8 +221,7 @@ def prepared_weights(weight, need_transposed, dtype=bf16):
     if need_transposed and ent[2] is None:
         Cout, Cin, k, _ = weight.shape
         wt = torch.empty((Cin, k * k * Cout), dtype=dtype, device=weight.device)
-        wd = weight.detach()
-        _chk(lib.cr_weight_transpose(_ctx(weight), _p(wd), _p(wt), Cout, k, Cin, int(dtype == f32)), "cr_weight_transpose")
+        _lib.call("cr_weight_transpose", weight.detach(), wt, Cout, k, Cin, int(dtype == f32))
         ent[2] = wt
     return ent[1], ent[2]
 
@@ -269,22 +230,19 @@ def prepared_weights(weight, need_transposed, dtype=bf16):
 # raw kernels
 # --------------------------------------------------------------------------
 def conv_fwd_raw(x, wb, Cout, k, stride, pad, bias=None, residual=None, relu=False, stats=None, out_f32=False):
-    _p = _Args()
     _need_cuda(x, "conv input")
     af = _af(x)
     assert x.is_contiguous() and x.dim() == 4 and wb.dtype == x.dtype and (residual is None or residual.dtype == x.dtype)
     N, H, W, Cin = x.shape
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     y = torch.empty((N, Ho, Wo, Cout), dtype=f32 if (out_f32 or af) else bf16, device=x.device)
-    lib = _lib.load()
-    _chk(lib.cr_conv2d_fwd(_ctx(x), _p(x), _p(wb), _p(y), N, H, W, Cin, Cout, k, stride, pad, _p(bias), _p(residual),
-                           int(relu), _p(stats), int(out_f32), af, _p(_w3(wb, af))), "cr_conv2d_fwd")
+    _lib.call("cr_conv2d_fwd", x, wb, y, N, H, W, Cin, Cout, k, stride, pad, bias, residual, int(relu), stats, int(out_f32), af,
+              _w3(wb, af))
     return y
 
 
 def conv_bwd_data_raw(dy, wt, in_shape, k, stride, pad, accumulate=None):
     """accumulate: a tensor of the result's shape that is added in the kernel's epilogue (see _GradSlot)"""
-    _p = _Args()
     N, H, W, Cin = in_shape
     Cout = dy.shape[3]
     assert wt.dtype == dy.dtype
@@ -292,10 +250,8 @@ def conv_bwd_data_raw(dy, wt, in_shape, k, stride, pad, accumulate=None):
     if accumulate is not None:
         assert tuple(accumulate.shape) == (N, H, W, Cin), "accumulate must have the input's shape"
         accumulate = accumulate.to(dy.dtype).contiguous()
-    lib = _lib.load()
     af = _af(dy)
-    _chk(lib.cr_conv2d_bwd_data(_ctx(dy), _p(dy), _p(wt), _p(dx), N, H, W, Cin, Cout, k, stride, pad, af, _p(_w3(wt, af)),
-                                _p(accumulate)), "cr_conv2d_bwd_data")
+    _lib.call("cr_conv2d_bwd_data", dy, wt, dx, N, H, W, Cin, Cout, k, stride, pad, af, _w3(wt, af), accumulate)
     return dx
 
 
@@ -371,25 +327,21 @@ def grad_sink(t):
 
 def conv_bwd_weight_raw(dy, x, k, stride, pad, sink=None, bias_acc=None):
     """dW (into `sink` when given).  bias_acc: f32 [Cout] buffer that additionally receives += sum_pixels dy (fused)."""
-    _p = _Args()
     N, H, W, Cin = x.shape
     Cout = dy.shape[3]
-    lib = _lib.load()
     af = _af(x)
     assert dy.dtype == x.dtype
     if bias_acc is not None:
         dw = sink if sink is not None else torch.empty((Cout, Cin, k, k), dtype=f32, device=x.device).contiguous(
             memory_format=torch.channels_last)
-        _chk(lib.cr_conv2d_bwd_weight_bias(_ctx(x), _p(dy), _p(x), _p(dw), _p(bias_acc), N, H, W, Cin, Cout, k, stride, pad,
-                                           int(sink is not None), af), "cr_conv2d_bwd_weight_bias")
+        _lib.call("cr_conv2d_bwd_weight_bias", dy, x, dw, bias_acc, N, H, W, Cin, Cout, k, stride, pad, int(sink is not None),
+                  af)
         return None if sink is not None else dw
     if sink is not None:
-        _chk(lib.cr_conv2d_bwd_weight(_ctx(x), _p(dy), _p(x), _p(sink), N, H, W, Cin, Cout, k, stride, pad, 1, af),
-             "cr_conv2d_bwd_weight")
+        _lib.call("cr_conv2d_bwd_weight", dy, x, sink, N, H, W, Cin, Cout, k, stride, pad, 1, af)
         return None
     dw = torch.empty((Cout, Cin, k, k), dtype=f32, device=x.device).contiguous(memory_format=torch.channels_last)
-    _chk(lib.cr_conv2d_bwd_weight(_ctx(x), _p(dy), _p(x), _p(dw), N, H, W, Cin, Cout, k, stride, pad, 0, af),
-         "cr_conv2d_bwd_weight")
+    _lib.call("cr_conv2d_bwd_weight", dy, x, dw, N, H, W, Cin, Cout, k, stride, pad, 0, af)
     return dw
 
 
@@ -401,11 +353,9 @@ class _ConvBN(torch.autograd.Function):
     def forward(ctx, x, weight, gamma, beta, residual, running_mean, running_var, stride, pad, relu, eps, momentum,
                 training, slots=((None, 0), (None, 0))):
         ctx.slots = slots
-        _p = _Args()
         Cout, Cin, k, _ = weight.shape
         dev = x.device
         af = _af(x)
-        lib = _lib.load()
         if training:
             wb, _ = prepared_weights(weight, x.requires_grad, x.dtype)
             _STATS_EPOCH[0] += 1
@@ -416,9 +366,8 @@ class _ConvBN(torch.autograd.Function):
             y_raw = conv_fwd_raw(x, wb, Cout, k, stride, pad, stats=stats)
             out = torch.empty_like(y_raw)
             mi = torch.empty((2, Cout), dtype=f32, device=dev)
-            _chk(lib.cr_bn_fwd(_ctx(x), _p(y_raw), _p(stats), nparts, _p(gamma.detach()), _p(beta.detach()), _p(residual),
-                               _p(out), M, Cout, int(relu), float(eps), float(momentum), _p(mi), _p(running_mean),
-                               _p(running_var), af), "cr_bn_fwd")
+            _lib.call("cr_bn_fwd", y_raw, stats, nparts, gamma.detach(), beta.detach(), residual, out, M, Cout, int(relu),
+                      float(eps), float(momentum), mi, running_mean, running_var, af)
         else:
             # frozen statistics with gradients enabled (freeze_bn fine-tuning; plain inference takes conv_bn_folded): the
             # BatchNorm folded into the convolution (cr_fold_bn) and ONE convolution with bias / residual / ReLU in its
@@ -428,11 +377,11 @@ class _ConvBN(torch.autograd.Function):
             K_ = weight.numel() // Cout
             wf32 = torch.empty((Cout, K_), dtype=f32, device=dev)
             bias_f = torch.empty((Cout,), dtype=f32, device=dev)
-            _chk(lib.cr_fold_bn(_ctx(x), _p(weight.detach()), _p(gamma.detach()), _p(beta.detach()), _p(running_mean),
-                                _p(running_var), float(eps), _p(wf32), _p(bias_f), Cout, K_, 1), "cr_fold_bn")
+            _lib.call("cr_fold_bn", weight.detach(), gamma.detach(), beta.detach(), running_mean, running_var, float(eps), wf32,
+                      bias_f, Cout, K_, 1)
             if x.dtype == bf16:
                 wf = torch.empty((Cout, K_), dtype=bf16, device=dev)
-                _chk(lib.cr_cast_f32_to_bf16(_ctx(x), _p(wf32), _p(wf), wf32.numel()), "cr_cast_f32_to_bf16")
+                _lib.call("cr_cast_f32_to_bf16", wf32, wf, wf32.numel())
             else:
                 wf = wf32
             out = conv_fwd_raw(x, wf, Cout, k, stride, pad, bias=bias_f, residual=residual, relu=relu)
@@ -451,7 +400,6 @@ class _ConvBN(torch.autograd.Function):
     def _backward_impl(ctx, dout, want_dx=None, want_dw=None):
         """want_dx / want_dw: overrides of needs_input_grad[0] / [1] (_RootConvBN computes the input gradients itself and then
         gets (dx_raw, dw, dgamma, dbeta) back instead of the argument-ordered tuple)"""
-        _p = _Args()
         x, weight, gamma, y_raw, out, mi = ctx.saved_tensors
         k, stride, pad, relu, training, has_res = ctx.cfg
         root = want_dx is not None
@@ -463,7 +411,6 @@ class _ConvBN(torch.autograd.Function):
         dev = x.device
         dout = dout.to(x.dtype).contiguous()
         M = y_raw.numel() // Cout
-        lib = _lib.load()
         sums = torch.empty((1025, 2, Cout), dtype=f32, device=dev)
         dx_raw = torch.empty_like(y_raw)
         dres = torch.empty_like(y_raw) if has_res else None
@@ -474,8 +421,8 @@ class _ConvBN(torch.autograd.Function):
             dgamma = torch.zeros((Cout,), dtype=f32, device=dev)
             dbeta = torch.zeros((Cout,), dtype=f32, device=dev)
             ret_g, ret_b = dgamma, dbeta
-        _chk(lib.cr_bn_bwd(_ctx(x), _p(dout), _p(out), _p(y_raw), _p(mi), _p(gamma.detach()), _p(sums), _p(dx_raw),
-                           _p(dres), _p(dgamma), _p(dbeta), M, Cout, int(relu), _af(x)), "cr_bn_bwd")
+        _lib.call("cr_bn_bwd", dout, out, y_raw, mi, gamma.detach(), sums, dx_raw, dres, dgamma, dbeta, M, Cout, int(relu),
+                  _af(x))
         (xslot, xi), (rslot, ri) = ctx.slots
         if rslot is not None and dres is not None:          # the residual's other consumer (a convolution) adds this
             _slot_put(rslot, dres)
@@ -501,14 +448,12 @@ class _ConvBN(torch.autograd.Function):
         dwf = conv_bwd_weight(g, x) and sum_p g into scratch in one launch, then cr_bn_frozen_unfold maps them to dw, dgamma
         and dbeta (into the parameters' gradient sinks when they have them).  root: _RootConvBN forms the children's
         gradients itself from g and ctx.frozen_wt."""
-        _p = _Args()
         x, weight, gamma, wf32, out, _ = ctx.saved_tensors
         k, stride, pad, relu, _, has_res = ctx.cfg
         running_mean, running_var, eps = ctx.frozen
         Cout, Cin = weight.shape[0], weight.shape[1]
         K_ = weight.numel() // Cout
         dev = x.device
-        lib = _lib.load()
         dout = dout.to(x.dtype).contiguous()
         g = relu_bwd(out, dout) if relu else dout
         (xslot, xi), (rslot, ri) = ctx.slots
@@ -520,7 +465,7 @@ class _ConvBN(torch.autograd.Function):
         if need_dx or root:
             wt = torch.empty((Cin, k * k * Cout), dtype=x.dtype, device=dev)        # [Cin][k*k][Cout]
             assert wt.numel() == wf32.numel()
-            _chk(lib.cr_weight_transpose(_ctx(x), _p(wf32), _p(wt), Cout, k, Cin, int(x.dtype == f32)), "cr_weight_transpose")
+            _lib.call("cr_weight_transpose", wf32, wt, Cout, k, Cin, int(x.dtype == f32))
             if root:
                 ctx.frozen_wt = wt
             elif xslot is not None and xi > 1:              # not the first consumer of x: leave the contribution in the slot
@@ -546,9 +491,8 @@ class _ConvBN(torch.autograd.Function):
             ret_g, ret_b = dgamma, dbeta
         dst = wsink if wsink is not None else dw
         assert dwf.numel() == Cout * K_ and (dst is None or dst.numel() == Cout * K_) and dgamma.numel() == Cout == dbeta.numel()
-        _chk(lib.cr_bn_frozen_unfold(_ctx(x), _p(dwf), _p(sg), _p(weight.detach()), _p(gamma.detach()), _p(running_mean),
-                                     _p(running_var), eps, _p(dst), int(wsink is not None), _p(dgamma), _p(dbeta), Cout, K_),
-             "cr_bn_frozen_unfold")
+        _lib.call("cr_bn_frozen_unfold", dwf, sg, weight.detach(), gamma.detach(), running_mean, running_var, eps, dst,
+                  int(wsink is not None), dgamma, dbeta, Cout, K_)
         if root:
             return g, dw, ret_g, ret_b
         return dx, dw, ret_g, ret_b, dres, None, None, None, None, None, None, None, None, None
@@ -623,15 +567,12 @@ _FOLD_REG = [None]          # a list while graphed.GraphedDenseEval captures: th
 def refresh_folds(reg):
     """re-fold (cr_fold_bn, in place) every registered BatchNorm whose inputs changed since its buffers were written; the
     check is host-side (version counters, weight / statistics epochs, storage addresses)"""
-    lib = None
     for e in reg:
         w, g, b, m, v = e["t"]
         tag = (w._version, g._version, b._version, m._version, v._version, _WEIGHT_EPOCH[0], _STATS_EPOCH[0], w.data_ptr(), m.data_ptr())
         if tag == e["tag"]:
             continue
-        lib = lib or _lib.load()
-        _chk(lib.cr_fold_bn(_ctx(e["wf"]), _p(w.detach()), _p(g.detach()), _p(b.detach()), _p(m), _p(v), e["eps"], _p(e["wf"]),
-                            _p(e["b"]), e["Cout"], e["K"], e["af"]), "cr_fold_bn")
+        _lib.call("cr_fold_bn", w.detach(), g.detach(), b.detach(), m, v, e["eps"], e["wf"], e["b"], e["Cout"], e["K"], e["af"])
         e["tag"] = tag
 
 
@@ -641,7 +582,6 @@ def conv_bn_folded(x, weight, gamma, beta, running_mean, running_var, stride=1, 
     Outside graph capture the folded copies are cached on the weight tensor (keyed by the version counters of the five
     tensors, the weight epoch and the statistics epoch); inside a capture they are recomputed, so that a replay follows
     weights that changed since."""
-    _p = _Args()
     _need_cuda(x, "conv input")
     weight = as_krsc(weight)
     Cout, _, k, _ = weight.shape
@@ -668,9 +608,8 @@ def conv_bn_folded(x, weight, gamma, beta, running_mean, running_var, stride=1, 
     if ent is None or ent[0] != tag:
         wf = torch.empty((Cout, K_), dtype=x.dtype, device=x.device)
         bias_f = torch.empty((Cout,), dtype=f32, device=x.device)
-        wd, gd, bd = weight.detach(), gamma.detach(), beta.detach()
-        _chk(_lib.load().cr_fold_bn(_ctx(x), _p(wd), _p(gd), _p(bd), _p(running_mean),
-                                    _p(running_var), float(eps), _p(wf), _p(bias_f), Cout, K_, _af(x)), "cr_fold_bn")
+        _lib.call("cr_fold_bn", weight.detach(), gamma.detach(), beta.detach(), running_mean, running_var, float(eps), wf, bias_f,
+                  Cout, K_, _af(x))
         ent = (tag, wf, bias_f)
         if not capturing:
             try:
@@ -696,10 +635,9 @@ def conv_bn_act(x, weight, gamma, beta, running_mean, running_var, stride=1, pad
 # --------------------------------------------------------------------------
 def relu_bwd(y, dy):
     """dy masked by the ReLU whose OUTPUT is y (one kernel); dy is cast to y's dtype first if it differs"""
-    _p = _Args()
     dy = _act_cast(dy, y.dtype)
     g = torch.empty_like(dy)
-    _chk(_lib.load().cr_relu_bwd(_ctx(y), _p(y.contiguous()), _p(dy), _p(g), y.numel(), _af(y)), "cr_relu_bwd")
+    _lib.call("cr_relu_bwd", y.contiguous(), dy, g, y.numel(), _af(y))
     return g
 
 
@@ -718,7 +656,6 @@ class _ConvBias(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        _p = _Args()
         x, weight, y = ctx.saved_tensors
         k, stride, pad, relu, has_bias = ctx.cfg
         g = dy.contiguous()
@@ -734,9 +671,7 @@ class _ConvBias(torch.autograd.Function):
             if not (ctx.needs_input_grad[1] and g.dtype == x.dtype):
                 # no weight-gradient launch to ride on (or an f32 upstream gradient): separate column sum
                 ws = torch.empty((1024, C), dtype=f32, device=g.device)
-                lib = _lib.load()
-                _chk(lib.cr_colsum_accum(_ctx(g), _p(g), int(g.dtype == f32), g.numel() // C, C, _p(ws), _p(acc)),
-                     "cr_colsum_accum")
+                _lib.call("cr_colsum_accum", g, int(g.dtype == f32), g.numel() // C, C, ws, acc)
                 acc = None
         g = g.to(x.dtype).contiguous()
         dx = None
@@ -838,26 +773,25 @@ def group_supported(xs, weights, stride=1):
 def conv_fwd_group_raw(xs, wbs, ys, Cin, Cout, k, pad, biases, relu):
     """cr_conv2d_fwd_group on prepared operands (module-level so that bench.py can bracket the launch with events)"""
     cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
-    _chk(_lib.load().cr_conv2d_fwd_group(
-        _ctx(xs[0]), len(xs), cast(_ptr_table(xs)), cast(_ptr_table(wbs)), cast(_ptr_table(ys)), cast(_int_table([x.shape[0] for x in xs])),
-        cast(_int_table([x.shape[1] for x in xs])), cast(_int_table([x.shape[2] for x in xs])), Cin, Cout, k, pad,
-        cast(_ptr_table(biases)), None, int(relu), _af(xs[0])), "cr_conv2d_fwd_group")
+    _lib.call("cr_conv2d_fwd_group", len(xs), cast(_ptr_table(xs)), cast(_ptr_table(wbs)), cast(_ptr_table(ys)),
+              cast(_int_table([x.shape[0] for x in xs])), cast(_int_table([x.shape[1] for x in xs])),
+              cast(_int_table([x.shape[2] for x in xs])), Cin, Cout, k, pad, cast(_ptr_table(biases)), None, int(relu),
+              _af(xs[0]), device=xs[0].device)
 
 
 def conv_bwd_data_group_raw(gs, wts, outs, shapes, Cin, Cout, k, pad, accs):
     cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
-    _chk(_lib.load().cr_conv2d_bwd_data_group(
-        _ctx(gs[0]), len(gs), cast(_ptr_table(gs)), cast(_ptr_table(wts)), cast(_ptr_table(outs)),
-        cast(_int_table([s_[0] for s_ in shapes])), cast(_int_table([s_[1] for s_ in shapes])), cast(_int_table([s_[2] for s_ in shapes])),
-        Cin, Cout, k, pad, _af(gs[0]), cast(_ptr_table(accs))), "cr_conv2d_bwd_data_group")
+    _lib.call("cr_conv2d_bwd_data_group", len(gs), cast(_ptr_table(gs)), cast(_ptr_table(wts)), cast(_ptr_table(outs)),
+              cast(_int_table([s_[0] for s_ in shapes])), cast(_int_table([s_[1] for s_ in shapes])),
+              cast(_int_table([s_[2] for s_ in shapes])), Cin, Cout, k, pad, _af(gs[0]), cast(_ptr_table(accs)),
+              device=gs[0].device)
 
 
 def conv_bwd_weight_group_raw(gs, xs, dws, dbs, Cin, Cout, k, pad):
     cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
-    _chk(_lib.load().cr_conv2d_bwd_weight_group(
-        _ctx(xs[0]), len(xs), cast(_ptr_table(gs)), cast(_ptr_table(xs)), cast(_ptr_table(dws)), cast(_ptr_table(dbs)),
-        cast(_int_table([x.shape[0] for x in xs])), cast(_int_table([x.shape[1] for x in xs])), cast(_int_table([x.shape[2] for x in xs])),
-        Cin, Cout, k, pad, 1), "cr_conv2d_bwd_weight_group")
+    _lib.call("cr_conv2d_bwd_weight_group", len(xs), cast(_ptr_table(gs)), cast(_ptr_table(xs)), cast(_ptr_table(dws)),
+              cast(_ptr_table(dbs)), cast(_int_table([x.shape[0] for x in xs])), cast(_int_table([x.shape[1] for x in xs])),
+              cast(_int_table([x.shape[2] for x in xs])), Cin, Cout, k, pad, 1, device=xs[0].device)
 
 
 # --------------------------------------------------------------------------
@@ -907,9 +841,7 @@ def _wino_plan(xs, ws, bs, k, pad):
 def wino_gemm_raw(V, U, M, T, cin, cout):
     """M[k] (T,cout) = V[k] (T,cin) @ U[k] (cout,cin)^T for the 16 transformed positions: one launch (module-level so that
     bench.py can bracket it with events)"""
-    _p = _Args()
-    _chk(_lib.load().cr_gemm_batched_f32(_ctx(V), _p(V), _p(U), _p(M), T, cin, cout, 16, T * cin, cout * cin, T * cout),
-         "cr_gemm_batched_f32")
+    _lib.call("cr_gemm_batched_f32", V, U, M, T, cin, cout, 16, T * cin, cout * cin, T * cout)
 
 
 def wino_conv3x3_group(srcs, w_krsc, dsts, bias, relu, accs, backward, keep_v=False):
@@ -918,8 +850,6 @@ def wino_conv3x3_group(srcs, w_krsc, dsts, bias, relu, accs, backward, keep_v=Fa
     keep_v: the transformed input goes to a tensor of its own, which is returned (the weight gradient multiplies the same
     planes: wino_wgrad_group(v_saved=...)), instead of the shared planes the next Winograd convolution overwrites."""
     cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
-    lib = _lib.load()
-    _p = _Args()
     assert w_krsc.dim() == 4 and w_krsc.shape[2:] == (3, 3) and w_krsc.is_contiguous(memory_format=torch.channels_last)
     O, C = w_krsc.shape[0], w_krsc.shape[1]              # logical (O, C, 3, 3) over physical [O][3][3][C]
     cin, cout = (O, C) if backward else (C, O)          # channels of the maps going in / coming out
@@ -929,13 +859,12 @@ def wino_conv3x3_group(srcs, w_krsc, dsts, bias, relu, accs, backward, keep_v=Fa
     U = U[:16 * O * C]
     if keep_v:
         V = torch.empty((16, T, cin), dtype=f32, device=dev)
-    ctx = _ctx(srcs[0])
-    _chk(lib.cr_wino_filter(ctx, _p(w_krsc), _p(U), O, C, int(backward)), "cr_wino_filter")
+    _lib.call("cr_wino_filter", w_krsc, U, O, C, int(backward))
     Ns, Hs, Ws = _int_table([x.shape[0] for x in srcs]), _int_table([x.shape[1] for x in srcs]), _int_table([x.shape[2] for x in srcs])
-    _chk(lib.cr_wino_input(ctx, len(srcs), cast(_ptr_table(srcs)), cast(Ns), cast(Hs), cast(Ws), cin, _p(V), T), "cr_wino_input")
+    _lib.call("cr_wino_input", len(srcs), cast(_ptr_table(srcs)), cast(Ns), cast(Hs), cast(Ws), cin, V, T)
     wino_gemm_raw(V, U, M, T, cin, cout)
-    _chk(lib.cr_wino_output(ctx, len(dsts), _p(M), cast(_ptr_table(dsts)), cast(Ns), cast(Hs), cast(Ws), cout, T, _p(bias), int(relu),
-                            cast(_ptr_table(accs)) if accs is not None else None), "cr_wino_output")
+    _lib.call("cr_wino_output", len(dsts), M, cast(_ptr_table(dsts)), cast(Ns), cast(Hs), cast(Ws), cout, T, bias, int(relu),
+              cast(_ptr_table(accs)) if accs is not None else None)
     return V if keep_v else None
 
 
@@ -955,30 +884,26 @@ def wino_wgrad_group(gs, xs, w_sink, b_sink, v_saved=None):
     the forward pass, dU[k] = dM[k]^T V[k] per transformed position (cr_linear_bwd_weight), dW += G^T dU G into the flat
     gradient; db += channel sums of dY.  45.8 instead of 103 GFLOP for the five pyramid levels of 4 images."""
     cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
-    lib = _lib.load()
-    _p = _Args()
     O, C = gs[0].shape[3], xs[0].shape[3]
     dev = xs[0].device
     T = sum(x.shape[0] * (x.shape[1] // 2) * (x.shape[2] // 2) for x in xs)
     V, M, U = _wino_buffers(T, C, O, dev)
-    ctx = _ctx(xs[0])
     Ns, Hs, Ws = _int_table([x.shape[0] for x in xs]), _int_table([x.shape[1] for x in xs]), _int_table([x.shape[2] for x in xs])
     if v_saved is not None:                 # the forward pass kept B^T x B of exactly these maps
         assert v_saved.shape == (16, T, C)
         V = v_saved
     else:
-        _chk(lib.cr_wino_input(ctx, len(xs), cast(_ptr_table(xs)), cast(Ns), cast(Hs), cast(Ws), C, _p(V), T), "cr_wino_input")
+        _lib.call("cr_wino_input", len(xs), cast(_ptr_table(xs)), cast(Ns), cast(Hs), cast(Ws), C, V, T)
     U.zero_()
     # the bias gradient rides on the dY transform (atomics over partial rows), or, deterministic, is a fixed-order column sum
     part = U[16 * O * C:] if b_sink is not None and not deterministic_on() else None
     if b_sink is not None and part is None:
         ws = torch.empty((1024, O), dtype=torch.float32, device=dev)
         for g in gs:
-            _chk(lib.cr_colsum_accum(ctx, _p(g), 1, g.numel() // O, O, _p(ws), _p(b_sink)), "cr_colsum_accum")
-    _chk(lib.cr_wino_dy(ctx, len(gs), cast(_ptr_table(gs)), cast(Ns), cast(Hs), cast(Ws), O, _p(M), T, _p(part)), "cr_wino_dy")
-    _chk(lib.cr_wgrad_batched_f32(ctx, _p(M), _p(V), _p(U), T, C, O, 16, T * O, T * C, O * C), "cr_wgrad_batched_f32")
-    _chk(lib.cr_wino_filter_grad(ctx, _p(U), _p(w_sink), O, C, _p(part), _p(b_sink) if part is not None else None),
-         "cr_wino_filter_grad")
+            _lib.call("cr_colsum_accum", g, 1, g.numel() // O, O, ws, b_sink)
+    _lib.call("cr_wino_dy", len(gs), cast(_ptr_table(gs)), cast(Ns), cast(Hs), cast(Ws), O, M, T, part)
+    _lib.call("cr_wgrad_batched_f32", M, V, U, T, C, O, 16, T * O, T * C, O * C)
+    _lib.call("cr_wino_filter_grad", U, w_sink, O, C, part, b_sink if part is not None else None)
 
 
 class _ConvBiasGroup(torch.autograd.Function):
@@ -992,7 +917,6 @@ class _ConvBiasGroup(torch.autograd.Function):
         over all pyramid levels at once); one gradient comes back and one ReLU backward covers all levels."""
         stacked = len(slots) == n + 1
         xs, ws, bs = args[:n], args[n:2 * n], args[2 * n:3 * n]
-        _p = _Args()
         Cout, Cin, k, _ = ws[0].shape
         dt = xs[0].dtype
         xs = [x.contiguous() for x in xs]
@@ -1039,9 +963,6 @@ class _ConvBiasGroup(torch.autograd.Function):
         ws, bs = ctx.refs
         saved = ctx.saved_tensors
         xs = saved[:n]
-        _p = _Args()
-        lib = _lib.load()
-        cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
         gs = {}
         if ctx.stacked is not None:
             live = list(range(n)) if dys[0] is not None else []
@@ -1150,12 +1071,10 @@ class _Pool2x(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, window, slot=(None, 0)):
         ctx.slot = slot
-        _p = _Args()
         _need_cuda(x, "pool input")
         N, H, W, C = x.shape
         y = torch.empty((N, H // 2, W // 2, C), dtype=x.dtype, device=x.device)
-        lib = _lib.load()
-        _chk(lib.cr_pool2x_fwd(_ctx(x), _p(x), _p(y), N, H, W, C, window, _af(x)), "cr_pool2x_fwd")
+        _lib.call("cr_pool2x_fwd", x, y, N, H, W, C, window, _af(x))
         ctx.window = window
         ctx.save_for_backward(x)
         ctx.set_materialize_grads(False)
@@ -1163,7 +1082,6 @@ class _Pool2x(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        _p = _Args()
         (x,) = ctx.saved_tensors
         N, H, W, C = x.shape
         xslot, xi = ctx.slot
@@ -1176,13 +1094,12 @@ class _Pool2x(torch.autograd.Function):
             acc = _slot_take(xslot)
             return (None if acc is None else acc.to(x.dtype)), None, None
         dx = torch.empty_like(x)
-        lib = _lib.load()
         dy = dy.to(x.dtype).contiguous()
         # the FIRST registered consumer of x (DLA: a level's input is pooled before its first convolution sees it) collects
         # what the others left in the slot, a later one folds the slot's content into its own result: added in the kernel
         acc = None if xslot is None else (_slot_take(xslot) if xi <= 1 else _slot_fold(xslot))
         acc = None if acc is None else acc.to(x.dtype).contiguous()
-        _chk(lib.cr_pool2x_bwd(_ctx(x), _p(x), _p(dy), _p(dx), N, H, W, C, ctx.window, _af(x), _p(acc)), "cr_pool2x_bwd")
+        _lib.call("cr_pool2x_bwd", x, dy, dx, N, H, W, C, ctx.window, _af(x), acc)
         if xslot is not None and xi > 1:
             _slot_put(xslot, dx)
             dx = None
@@ -1192,24 +1109,20 @@ class _Pool2x(torch.autograd.Function):
 class _Pool3s2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        _p = _Args()
         _need_cuda(x, "pool input")
         N, H, W, C = x.shape
         y = torch.empty((N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), dtype=x.dtype, device=x.device)
-        lib = _lib.load()
-        _chk(lib.cr_maxpool3x3s2_fwd(_ctx(x), _p(x), _p(y), N, H, W, C, _af(x)), "cr_maxpool3x3s2_fwd")
+        _lib.call("cr_maxpool3x3s2_fwd", x, y, N, H, W, C, _af(x))
         ctx.save_for_backward(x)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        _p = _Args()
         (x,) = ctx.saved_tensors
         N, H, W, C = x.shape
         dx = torch.empty_like(x)
-        lib = _lib.load()
         dy = dy.to(x.dtype).contiguous()
-        _chk(lib.cr_maxpool3x3s2_bwd(_ctx(x), _p(x), _p(dy), _p(dx), N, H, W, C, _af(x)), "cr_maxpool3x3s2_bwd")
+        _lib.call("cr_maxpool3x3s2_bwd", x, dy, dx, N, H, W, C, _af(x))
         return dx
 
 
@@ -1232,25 +1145,21 @@ class _UpsampleAdd(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lat, top, slot=(None, 0)):
         ctx.slot = slot
-        _p = _Args()
         _need_cuda(lat, "upsample_add input")
         N, H, W, C = lat.shape
         assert tuple(top.shape) == (N, H // 2, W // 2, C)
         y = torch.empty_like(lat)
-        lib = _lib.load()
         assert lat.dtype == top.dtype
-        _chk(lib.cr_upsample2x_add(_ctx(lat), _p(lat), _p(top), _p(y), N, H, W, C, _af(lat)), "cr_upsample2x_add")
+        _lib.call("cr_upsample2x_add", lat, top, y, N, H, W, C, _af(lat))
         ctx.shape = (N, H, W, C)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        _p = _Args()
         N, H, W, C = ctx.shape
         dy = dy.contiguous()
         dtop = torch.empty((N, H // 2, W // 2, C), dtype=dy.dtype, device=dy.device)
-        lib = _lib.load()
-        _chk(lib.cr_sum2x2(_ctx(dy), _p(dy), _p(dtop), N, H, W, C, _af(dy)), "cr_sum2x2")
+        _lib.call("cr_sum2x2", dy, dtop, N, H, W, C, _af(dy))
         tslot, ti = ctx.slot
         if tslot is not None:                                # the coarser level's output convolution adds this (see _GradSlot)
             _slot_put(tslot, dtop)
@@ -1266,7 +1175,6 @@ def upsample2x_add(lat, top):
 def preprocess(images_u8, mean, std, dtype=None):
     """(N,3,H,W) uint8 -> normalised NHWC with 8 (bf16) or 4 (f32) channels (3 real + zeros) in the activation dtype of the process
     (set_precision) unless `dtype` says otherwise: this call decides the precision of everything downstream."""
-    _p = _Args()
     _need_cuda(images_u8, "images")
     assert images_u8.dtype == torch.uint8 and images_u8.is_contiguous()
     N, _, H, W = images_u8.shape
@@ -1274,9 +1182,7 @@ def preprocess(images_u8, mean, std, dtype=None):
     y = torch.empty((N, H, W, 8 if dt == bf16 else 4), dtype=dt, device=images_u8.device)     # one 16-B chunk per pixel
     m = (ctypes.c_float * 3)(*[float(v) for v in mean])
     s = (ctypes.c_float * 3)(*[float(v) for v in std])
-    lib = _lib.load()
-    _chk(lib.cr_preprocess(_ctx(images_u8), _p(images_u8), _p(y), N, H, W, ctypes.cast(m, ctypes.c_void_p),
-                           ctypes.cast(s, ctypes.c_void_p), _af(y)), "cr_preprocess")
+    _lib.call("cr_preprocess", images_u8, y, N, H, W, ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), _af(y))
     return y
 
 
@@ -1306,7 +1212,6 @@ class _ROIAlign(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rois, scales, out_size, slots, *feats):
-        _p = _Args()
         _need_cuda(rois, "rois")
         C = feats[0].shape[3]
         R = rois.shape[0]
@@ -1314,10 +1219,9 @@ class _ROIAlign(torch.autograd.Function):
         assert all(f.dtype == dt and f.is_contiguous() for f in feats)
         out = torch.empty((R, out_size, out_size, C), dtype=dt, device=rois.device)
         n, ptrs, Hs, Ws, sc, cast = _pyr_args(feats, scales)
-        lib = _lib.load()
         rois = rois.contiguous()
-        _chk(lib.cr_roi_align_fwd(_ctx(rois), cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, _p(rois), R, out_size,
-                                  out_size, _p(out), _af(out)), "cr_roi_align_fwd")
+        _lib.call("cr_roi_align_fwd", cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, rois, R, out_size, out_size, out,
+                  _af(out))
         ctx.cfg = (scales, out_size, [tuple(f.shape) for f in feats], dt)
         ctx.slots = slots
         # claimed (popped): a second RoIAlign over the same maps takes the ordinary path and autograd adds the two
@@ -1327,7 +1231,6 @@ class _ROIAlign(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        _p = _Args()
         (rois,) = ctx.saved_tensors
         scales, out_size, shapes, dt = ctx.cfg
         C = shapes[0][3]
@@ -1348,14 +1251,13 @@ class _ROIAlign(torch.autograd.Function):
                 grads.append(flat[off:off + int(s[0] * s[1] * s[2] * s[3])].view(s))
                 off += n_
         n, ptrs, Hs, Ws, sc, cast = _pyr_args(grads, scales)
-        lib = _lib.load()
         dout = dout.to(dt).contiguous()
         if tiles:
-            _chk(lib.cr_roi_align_bwd_set(_ctx(rois), cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, int(shapes[0][0]), _p(rois),
-                                          rois.shape[0], out_size, out_size, _p(dout), _af(dout)), "cr_roi_align_bwd_set")
+            _lib.call("cr_roi_align_bwd_set", cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, int(shapes[0][0]), rois,
+                      rois.shape[0], out_size, out_size, dout, _af(dout))
         else:
-            _chk(lib.cr_roi_align_bwd(_ctx(rois), cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, _p(rois), rois.shape[0],
-                                      out_size, out_size, _p(dout), _af(dout)), "cr_roi_align_bwd")
+            _lib.call("cr_roi_align_bwd", cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, rois, rois.shape[0], out_size,
+                      out_size, dout, _af(dout))
         res = []
         for g, (slot, _i) in zip(grads, ctx.slots):
             g = g if dt == f32 else g.to(dt)
@@ -1404,7 +1306,6 @@ def roi_align_pyramid(feats, rois, scales, out_size):
 class _CubeLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, dxy, zr, dr, Ra, u, consts, flags):
-        _p = _Args()
         _need_cuda(dxy, "cube head outputs")
         n = dxy.shape[0]
         ins = [t.contiguous().to(f32) for t in (dxy, zr, dr, Ra.reshape(n, 9), u)] + \
@@ -1412,9 +1313,7 @@ class _CubeLoss(torch.autograd.Function):
         arr = (ctypes.c_void_p * 13)(*[t.data_ptr() for t in ins])
         losses = torch.empty((n, 5), dtype=f32, device=dxy.device)
         dec = torch.empty((n, 17), dtype=f32, device=dxy.device)
-        lib = _lib.load()
-        _chk(lib.cr_cube_loss_fwd(_ctx(dxy), ctypes.cast(arr, ctypes.c_void_p), n, *flags, _p(losses), _p(dec)),
-             "cr_cube_loss_fwd")
+        _lib.call("cr_cube_loss_fwd", ctypes.cast(arr, ctypes.c_void_p), n, *flags, losses, dec)
         ctx.ins, ctx.flags = ins, flags
         ctx.set_materialize_grads(False)       # outputs nobody differentiates arrive as None, not as zero fills
         ctx.mark_non_differentiable(dec)
@@ -1422,7 +1321,6 @@ class _CubeLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gl, _gdec):
-        _p = _Args()
         ins, flags = ctx.ins, ctx.flags
         n = ins[0].shape[0]
         dev = ins[0].device
@@ -1432,9 +1330,8 @@ class _CubeLoss(torch.autograd.Function):
         g_dr = torch.empty((n, 3), dtype=f32, device=dev)
         g_Ra = torch.empty((n, 3, 3), dtype=f32, device=dev)
         g_u = torch.empty((n,), dtype=f32, device=dev)
-        lib = _lib.load()
-        _chk(lib.cr_cube_loss_bwd(_ctx(ins[0]), ctypes.cast(arr, ctypes.c_void_p), n, *flags, _p(gl.contiguous()),
-                                  _p(g_dxy), _p(g_zr), _p(g_dr), _p(g_Ra), _p(g_u)), "cr_cube_loss_bwd")
+        _lib.call("cr_cube_loss_bwd", ctypes.cast(arr, ctypes.c_void_p), n, *flags, gl.contiguous(), g_dxy, g_zr, g_dr, g_Ra,
+                  g_u)
         return g_dxy, g_zr, g_dr, g_Ra, g_u, None, None
 
 
@@ -1455,11 +1352,9 @@ def prepared_fc_weight(weight, chw=None, dtype=bf16, need_transposed=False):
     wp (O,K) and, when asked, wt (K,O) for the backward-data GEMM.  chw = (C,H,W): the columns are re-ordered from the
     checkpoint's (c,h,w) flattening to (h,w,c) for NHWC-flattened RoI features.  f32 without a permutation: wp is the
     weight itself."""
-    _p = _Args()
     attr = "_cr_fccache" if dtype == bf16 else "_cr_fccache32"
     ent = getattr(weight, attr, None)
     tag = (weight._version, _WEIGHT_EPOCH[0], weight.data_ptr(), chw)
-    lib = _lib.load()
     O, K = weight.shape
     if ent is None or ent[0] != tag:
         if dtype == f32 and chw is None:
@@ -1468,8 +1363,7 @@ def prepared_fc_weight(weight, chw=None, dtype=bf16, need_transposed=False):
             C, HW = (chw[0], chw[1] * chw[2]) if chw is not None else (K, 1)
             assert C * HW == K
             wp = torch.empty((O, K), dtype=dtype, device=weight.device)
-            _chk(lib.cr_fc_weight_prepare(_ctx(weight), _p(weight.detach().contiguous()), _p(wp), O, C, HW, int(dtype == f32)),
-                 "cr_fc_weight_prepare")
+            _lib.call("cr_fc_weight_prepare", weight.detach().contiguous(), wp, O, C, HW, int(dtype == f32))
         ent = [tag, wp, None]
         try:
             setattr(weight, attr, ent)
@@ -1477,7 +1371,7 @@ def prepared_fc_weight(weight, chw=None, dtype=bf16, need_transposed=False):
             pass
     if need_transposed and ent[2] is None:
         wt = torch.empty((K, O), dtype=dtype, device=weight.device)
-        _chk(lib.cr_transpose2d(_ctx(weight), _p(ent[1].contiguous()), _p(wt), O, K, int(dtype == f32)), "cr_transpose2d")
+        _lib.call("cr_transpose2d", ent[1].contiguous(), wt, O, K, int(dtype == f32))
         ent[2] = wt
     return (ent[1], ent[2]) if need_transposed else ent[1]
 
@@ -1487,17 +1381,15 @@ def _act_cast(t, dtype):
     if t.dtype == dtype:
         return t.contiguous()
     if dtype == bf16 and t.dtype == f32:
-        _p = _Args()
         tc = t.contiguous()
         out = torch.empty(tc.shape, dtype=bf16, device=t.device)
-        _chk(_lib.load().cr_cast_f32_to_bf16(_ctx(t), _p(tc), _p(out), tc.numel()), "cr_cast_f32_to_bf16")
+        _lib.call("cr_cast_f32_to_bf16", tc, out, tc.numel())
         return out
     return t.to(dtype).contiguous()
 
 
 def linear_fwd_raw(x, w, bias, out_f32=False, relu=False):
     """y (R,O) = x (R,K) @ w (O,K)^T + bias on the MFMA; x / w in the same activation dtype, bias f32 or None"""
-    _p = _Args()
     af = _af(x)
     R, K = x.shape
     O = w.shape[0]
@@ -1505,30 +1397,26 @@ def linear_fwd_raw(x, w, bias, out_f32=False, relu=False):
         raise _lib.CrError(f"linear: the GEMM kernels need O and K multiples of 16 (got {O}x{K}); use linear_cat for predictors")
     assert w.dtype == x.dtype and x.is_contiguous() and w.is_contiguous()
     y = torch.empty((R, O), dtype=f32 if (out_f32 or af) else bf16, device=x.device)
-    _chk(_lib.load().cr_linear_fwd(_ctx(x), _p(x), _p(w), _p(bias), _p(y), R, K, O, int(relu), int(out_f32), af,
-                                   _p(_w3(w, af))), "cr_linear_fwd")
+    _lib.call("cr_linear_fwd", x, w, bias, y, R, K, O, int(relu), int(out_f32), af, _w3(w, af))
     return y
 
 
 def linear_bwd_data_raw(dy, wt):
-    _p = _Args()
     R, O = dy.shape
     K = wt.shape[0]
     assert wt.dtype == dy.dtype and dy.is_contiguous() and wt.is_contiguous()
     dx = torch.empty((R, K), dtype=dy.dtype, device=dy.device)
     af = _af(dy)
-    _chk(_lib.load().cr_linear_bwd_data(_ctx(dy), _p(dy), _p(wt), _p(dx), R, K, O, af, _p(_w3(wt, af))), "cr_linear_bwd_data")
+    _lib.call("cr_linear_bwd_data", dy, wt, dx, R, K, O, af, _w3(wt, af))
     return dx
 
 
 def linear_bwd_weight_raw(dy, x, dw, dbias, accumulate):
     """dw (O,K) f32 (+)= dy^T x; dbias (O) f32 += column sums of dy (None: not wanted)"""
-    _p = _Args()
     R, O = dy.shape
     K = x.shape[1]
     assert dy.dtype == x.dtype and dy.is_contiguous() and x.is_contiguous() and dw.dtype == f32
-    _chk(_lib.load().cr_linear_bwd_weight(_ctx(dy), _p(dy), _p(x), _p(dw), _p(dbias), R, K, O, int(accumulate), _af(x)),
-         "cr_linear_bwd_weight")
+    _lib.call("cr_linear_bwd_weight", dy, x, dw, dbias, R, K, O, int(accumulate), _af(x))
 
 
 class _Linear(torch.autograd.Function):
@@ -1545,11 +1433,9 @@ class _Linear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        _p = _Args()
         xc, yr = ctx.saved_tensors
         weight, bias, chw = ctx.refs
         dt = xc.dtype
-        lib = _lib.load()
         O, K = weight.shape
         C, HW = (chw[0], chw[1] * chw[2]) if chw is not None else (K, 1)
         dy = _act_cast(dy, dt)
@@ -1577,10 +1463,10 @@ class _Linear(torch.autograd.Function):
                 if acc is None:
                     acc = torch.zeros((O, K), dtype=f32, device=dy.device)
                     dw = acc
-                _chk(lib.cr_fc_grad_accum(_ctx(dy), _p(g), _p(acc), O, C, HW, 1), "cr_fc_grad_accum")
+                _lib.call("cr_fc_grad_accum", g, acc, O, C, HW, 1)
         elif want_db:
             ws = torch.empty((1024, O), dtype=f32, device=dy.device)
-            _chk(lib.cr_colsum_accum(_ctx(dy), _p(dy), int(dt == f32), dy.shape[0], O, _p(ws), _p(bacc)), "cr_colsum_accum")
+            _lib.call("cr_colsum_accum", dy, int(dt == f32), dy.shape[0], O, ws, bacc)
         return dx, dw, db, None, None
 
 
@@ -1634,7 +1520,7 @@ class _CatPlan:
         tag = _WEIGHT_EPOCH[0]
         if self.tag != tag:
             t, nd, tot = self.fwd_table
-            _chk(_lib.load().cr_multi_seg(_ctx(self.W), _lib.ptr(t), nd, tot, 0), "cr_multi_seg")
+            _lib.call("cr_multi_seg", t, nd, tot, 0)
             self.tag, self.compute, self.wt = tag, {}, {}
 
     def weight(self, dtype):
@@ -1645,10 +1531,9 @@ class _CatPlan:
 
     def weight_t(self, dtype):
         if dtype not in self.wt:
-            _p = _Args()
             Wc = self.weight(dtype)
             wt = torch.empty((self.K, self.Op), dtype=dtype, device=Wc.device)
-            _chk(_lib.load().cr_transpose2d(_ctx(Wc), _p(Wc), _p(wt), self.Op, self.K, int(dtype == f32)), "cr_transpose2d")
+            _lib.call("cr_transpose2d", Wc, wt, self.Op, self.K, int(dtype == f32))
             self.wt[dtype] = wt
         return self.wt[dtype]
 
@@ -1706,7 +1591,7 @@ class _LinearCat(torch.autograd.Function):
         linear_bwd_weight_raw(dy, xc, plan.dW, plan.db, accumulate=False)
         if plan.sinks:
             t, nd, tot = plan.bwd_table
-            _chk(_lib.load().cr_multi_seg(_ctx(plan.dW), _lib.ptr(t), nd, tot, 1), "cr_multi_seg")
+            _lib.call("cr_multi_seg", t, nd, tot, 1)
             return (dx, None) + (None,) * (2 * n)
         gw = [plan.dW[plan.offs[i]:plan.offs[i + 1]].clone() for i in range(n)]
         gb = [plan.db[plan.offs[i]:plan.offs[i + 1]].clone() for i in range(n)]
@@ -1728,7 +1613,6 @@ def linear_cat(x, weights, biases):
 # --------------------------------------------------------------------------
 def nms_grouped(boxes, counts, thresh):
     """boxes (G,maxn,4) f32 sorted by descending score per group; counts (G,) int32 -> keep (G,maxn) bool."""
-    _p = _Args()
     _need_cuda(boxes, "boxes")
     G, maxn, _ = boxes.shape
     keep = torch.zeros((G, maxn), dtype=torch.uint8, device=boxes.device)
@@ -1736,9 +1620,7 @@ def nms_grouped(boxes, counts, thresh):
         return keep.bool()
     words = (maxn + 63) // 64
     ws = torch.empty((G * maxn * words,), dtype=torch.int64, device=boxes.device)
-    lib = _lib.load()
-    _chk(lib.cr_nms_grouped(_ctx(boxes), _p(boxes.contiguous()), _p(counts.to(torch.int32).contiguous()), G, maxn,
-                            float(thresh), _p(ws), _p(keep)), "cr_nms_grouped")
+    _lib.call("cr_nms_grouped", boxes.contiguous(), counts.to(torch.int32).contiguous(), G, maxn, float(thresh), ws, keep)
     return keep.bool()
 
 
@@ -1748,9 +1630,7 @@ def det_select(logits, deltas, prop_boxes, objectness, img_hw, B, P, K, weights,
     (B*P, >= K+1), deltas (B*P, 4K or 4), prop_boxes (B*P,4), objectness (B*P) or None, img_hw (B,2) float.
     -> boxes (B,D,4), scores (B,D), classes (B,D) int64, rows (B,D) int64 (proposal slot inside the image),
     scores_full (B,D,K), count (B,2) int32 = [detections, overflow flag]."""
-    _p = _Args()
     _need_cuda(logits, "box head logits")
-    lib = _lib.load()
     dev = logits.device
     # column slices of the predictor GEMM's output are taken as they are (row stride = its width): no copies
     rows_ok = lambda t: t.dtype == f32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]
@@ -1761,8 +1641,8 @@ def det_select(logits, deltas, prop_boxes, objectness, img_hw, B, P, K, weights,
     nreg = 1 if dl.shape[1] < 4 * K else K
     S = torch.empty((B, P * K), dtype=f32, device=dev)
     ncand = torch.empty((B + 2,), dtype=torch.int32, device=dev)
-    _chk(lib.cr_det_scores(_ctx(lg), _lib.P(lg.data_ptr()), ldl, _lib.P(dl.data_ptr()), ldd, _p(pb), _p(objectness), B, P, K, nreg, float(score_thresh),
-                           _p(S), _p(ncand)), "cr_det_scores")
+    _lib.call("cr_det_scores", _lib.P(lg.data_ptr()), ldl, _lib.P(dl.data_ptr()), ldd, pb, objectness, B, P, K, nreg,
+              float(score_thresh), S, ncand)
     Kc = min(int(max_candidates), P * K)
     val, idx = topk(S, Kc)
     boxes = torch.empty((B, Kc, 4), dtype=f32, device=dev)
@@ -1771,20 +1651,20 @@ def det_select(logits, deltas, prop_boxes, objectness, img_hw, B, P, K, weights,
     counts = torch.empty((B,), dtype=torch.int32, device=dev)
     w4 = (_ct.c_float * 4)(*[float(w) for w in weights])
     val, idx = val.contiguous(), idx.contiguous()
-    _chk(lib.cr_det_gather(_ctx(lg), _p(val), _p(idx), _lib.P(dl.data_ptr()), ldd, _p(pb), _p(img_hw.float().contiguous()), B, P, K, nreg, Kc,
-                           w4, float(scale_clamp), _p(boxes), _p(cls), _p(row), _p(counts)), "cr_det_gather")
+    _lib.call("cr_det_gather", val, idx, _lib.P(dl.data_ptr()), ldd, pb, img_hw.float().contiguous(), B, P, K, nreg, Kc, w4,
+              float(scale_clamp), boxes, cls, row, counts)
     words = (Kc + 63) // 64
     ws = torch.empty((B * Kc * words,), dtype=torch.int64, device=dev)
     keep = torch.empty((B, Kc), dtype=torch.uint8, device=dev)
-    _chk(lib.cr_nms_grouped_cls(_ctx(lg), _p(boxes), _p(cls), _p(counts), B, Kc, float(nms_thresh), _p(ws), _p(keep)), "cr_nms_grouped_cls")
+    _lib.call("cr_nms_grouped_cls", boxes, cls, counts, B, Kc, float(nms_thresh), ws, keep)
     D = int(detections)
     ob = torch.empty((B, D, 4), dtype=f32, device=dev)
     osc = torch.empty((B, D), dtype=f32, device=dev)
     oi = torch.empty((2, B, D), dtype=torch.int64, device=dev)
     ofull = torch.empty((B, D, K), dtype=f32, device=dev)
     ocnt = torch.empty((B, 2), dtype=torch.int32, device=dev)
-    _chk(lib.cr_det_pick(_ctx(lg), _p(keep), _p(counts), _p(ncand), _p(val), _p(boxes), _p(cls), _p(row), _lib.P(lg.data_ptr()), ldl, B, P, K, Kc,
-                         D, _p(ob), _p(osc), _p(oi[0]), _p(oi[1]), _p(ofull), _p(ocnt)), "cr_det_pick")
+    _lib.call("cr_det_pick", keep, counts, ncand, val, boxes, cls, row, _lib.P(lg.data_ptr()), ldl, B, P, K, Kc, D, ob, osc,
+              oi[0], oi[1], ofull, ocnt)
     return ob, osc, oi[0], oi[1], ofull, ocnt
 
 
@@ -1801,7 +1681,6 @@ def _f4(vals):
 def rpn_decode_select(anchors, deltas, idx, scores, weights, scale_clamp, img_hw, min_size):
     """anchors (A,4), deltas (B,A,4), idx (B,S) int64 (-1 = empty), scores (B,S), img_hw (B,2) ->
     boxes (B,S,4) clipped, nms_boxes (B,S,4) (zero where invalid), valid (B,S) bool."""
-    _p = _Args()
     _need_cuda(deltas, "deltas")
     B, A = deltas.shape[0], anchors.shape[0]
     S = idx.shape[1]
@@ -1809,17 +1688,14 @@ def rpn_decode_select(anchors, deltas, idx, scores, weights, scale_clamp, img_hw
     boxes = torch.empty((B, S, 4), dtype=f32, device=dev)
     nmsb = torch.empty((B, S, 4), dtype=f32, device=dev)
     valid = torch.empty((B, S), dtype=torch.uint8, device=dev)
-    lib = _lib.load()
-    _chk(lib.cr_rpn_decode_select(_ctx(deltas), _p(anchors.contiguous()), _p(deltas.contiguous()), _p(idx.contiguous()),
-                                  _p(scores.contiguous()), B, A, S, _f4(weights), float(scale_clamp), _p(img_hw.contiguous()),
-                                  float(min_size), _p(boxes), _p(nmsb), _p(valid)), "cr_rpn_decode_select")
+    _lib.call("cr_rpn_decode_select", anchors.contiguous(), deltas.contiguous(), idx.contiguous(), scores.contiguous(), B, A, S,
+              _f4(weights), float(scale_clamp), img_hw.contiguous(), float(min_size), boxes, nmsb, valid)
     return boxes, nmsb, valid.bool()
 
 
 def box_match(boxes, gt_boxes, gt_classes, want_best=False):
     """boxes (R,4) or (B,R,4); gt_boxes (B,G,4); gt_classes (B,G) int64 -> max_iou (B,R), argmax (B,R) int32,
     max_ioa (B,R), best (B,G) int64 (packed, see include/cr3dod.h) or None."""
-    _p = _Args()
     _need_cuda(gt_boxes, "gt_boxes")
     B, G = gt_classes.shape
     per_image = boxes.dim() == 3
@@ -1829,14 +1705,12 @@ def box_match(boxes, gt_boxes, gt_classes, want_best=False):
     am = torch.empty((B, R), dtype=torch.int32, device=dev)
     ma = torch.empty((B, R), dtype=f32, device=dev)
     best = torch.empty((B, G), dtype=torch.int64, device=dev) if want_best else None
-    lib = _lib.load()
-    _chk(lib.cr_box_match(_ctx(gt_boxes), _p(boxes.contiguous()), int(per_image), _p(gt_boxes.contiguous()),
-                          _p(gt_classes.contiguous()), B, R, G, _p(mi), _p(am), _p(ma), _p(best)), "cr_box_match")
+    _lib.call("cr_box_match", boxes.contiguous(), int(per_image), gt_boxes.contiguous(), gt_classes.contiguous(), B, R, G, mi,
+              am, ma, best)
     return mi, am, ma, best
 
 
 def rpn_label(anchors, gt_boxes, gt_classes, max_iou, best, expo, lo, hi, labels3, eps):
-    _p = _Args()
     B, A = max_iou.shape
     G = gt_classes.shape[1]
     dev = max_iou.device
@@ -1844,29 +1718,23 @@ def rpn_label(anchors, gt_boxes, gt_classes, max_iou, best, expo, lo, hi, labels
     out = torch.empty((B, A), dtype=torch.int32, device=dev)
     miou = torch.empty((B, A), dtype=f32, device=dev)
     keys = torch.empty((2, B, A), dtype=f32, device=dev)
-    lib = _lib.load()
-    _chk(lib.cr_rpn_label(_ctx(max_iou), _p(anchors.contiguous()), _p(gt_boxes.contiguous()), _p(gt_classes.contiguous()),
-                          _p(max_iou), _p(best), _p(expo.contiguous()), B, A, G, float(lo), float(hi),
-                          (_ct.c_int * 3)(*[int(v) for v in labels3]), float(eps), _p(labels_pre), _p(out), _p(miou),
-                          _p(keys)), "cr_rpn_label")
+    _lib.call("cr_rpn_label", anchors.contiguous(), gt_boxes.contiguous(), gt_classes.contiguous(), max_iou, best,
+              expo.contiguous(), B, A, G, float(lo), float(hi), (_ct.c_int * 3)(*[int(v) for v in labels3]), float(eps),
+              labels_pre, out, miou, keys)
     return labels_pre, out, miou, keys
 
 
 def rpn_scatter(out, pos_idx, pos_key, neg_idx, neg_key, n_s, ioa, ignore_thresh):
     """in place on out (B,A) int32."""
-    _p = _Args()
     B, A = out.shape
-    lib = _lib.load()
-    _chk(lib.cr_rpn_scatter(_ctx(out), _p(pos_idx.contiguous()), _p(pos_key.contiguous()), pos_idx.shape[1],
-                            _p(neg_idx.contiguous()), _p(neg_key.contiguous()), neg_idx.shape[1], int(n_s),
-                            _p(ioa.contiguous()), float(ignore_thresh), B, A, _p(out)), "cr_rpn_scatter")
+    _lib.call("cr_rpn_scatter", pos_idx.contiguous(), pos_key.contiguous(), pos_idx.shape[1], neg_idx.contiguous(),
+              neg_key.contiguous(), neg_idx.shape[1], int(n_s), ioa.contiguous(), float(ignore_thresh), B, A, out)
     return out
 
 
 class _RPNLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, deltas, anchors, labels, midx, gt_boxes, weights):
-        _p = _Args()
         B, A = logits.shape
         G = gt_boxes.shape[1]
         dev = logits.device
@@ -1875,11 +1743,9 @@ class _RPNLoss(torch.autograd.Function):
         sums = torch.empty((6,), dtype=f32, device=dev)
         dl = torch.empty((B, A), dtype=f32, device=dev)
         dd = torch.empty((B, A, 4), dtype=f32, device=dev)
-        lib = _lib.load()
-        _chk(lib.cr_rpn_loss(_ctx(logits), _p(logits.detach().float().contiguous()), _p(deltas.detach().float().contiguous()),
-                             _p(anchors.contiguous()), _p(labels.contiguous()), _p(midx.contiguous()),
-                             _p(gt_boxes.contiguous()), B, A, G, _f4(weights), _p(ws), _p(sums), _p(dl), _p(dd)),
-             "cr_rpn_loss")
+        _lib.call("cr_rpn_loss", logits.detach().float().contiguous(), deltas.detach().float().contiguous(),
+                  anchors.contiguous(), labels.contiguous(), midx.contiguous(), gt_boxes.contiguous(), B, A, G, _f4(weights),
+                  ws, sums, dl, dd)
         ctx.save_for_backward(dl, dd)
         ctx.set_materialize_grads(False)       # outputs nobody differentiates arrive as None, not as zero fills
         ctx.mark_non_differentiable(sums)
@@ -1897,22 +1763,19 @@ def rpn_loss(logits, deltas, anchors, labels, midx, gt_boxes, weights):
 
 
 def roi_label(max_iou, argmax, max_ioa, valid, gt_classes, expo, K, thr, ignore_thresh, eps):
-    _p = _Args()
     B, R = max_iou.shape
     dev = max_iou.device
     cls = torch.empty((B, R), dtype=torch.int64, device=dev)
     miou = torch.empty((B, R), dtype=f32, device=dev)
     keys = torch.empty((2, B, R), dtype=f32, device=dev)
-    lib = _lib.load()
-    _chk(lib.cr_roi_label(_ctx(max_iou), _p(max_iou), _p(argmax), _p(max_ioa), _p(valid.to(torch.uint8).contiguous()),
-                          _p(gt_classes.contiguous()), _p(expo.contiguous()), B, R, gt_classes.shape[1], int(K), float(thr),
-                          float(ignore_thresh), float(eps), _p(cls), _p(miou), _p(keys)), "cr_roi_label")
+    _lib.call("cr_roi_label", max_iou, argmax, max_ioa, valid.to(torch.uint8).contiguous(), gt_classes.contiguous(),
+              expo.contiguous(), B, R, gt_classes.shape[1], int(K), float(thr), float(ignore_thresh), float(eps), cls, miou,
+              keys)
     return cls, miou, keys
 
 
 def roi_compact(fg_idx, fg_key, bg_idx, bg_key, n_s, boxes, cls, argmax):
     """-> boxes (B,n_s,4), valid (B,n_s) bool, classes (B,n_s) int64, gt_idx (B,n_s) int64, counts (B,2) int32."""
-    _p = _Args()
     B, R = cls.shape
     dev = cls.device
     ob = torch.empty((B, n_s, 4), dtype=f32, device=dev)
@@ -1920,17 +1783,14 @@ def roi_compact(fg_idx, fg_key, bg_idx, bg_key, n_s, boxes, cls, argmax):
     oc = torch.empty((B, n_s), dtype=torch.int64, device=dev)
     og = torch.empty((B, n_s), dtype=torch.int64, device=dev)
     counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    _chk(lib.cr_roi_compact(_ctx(cls), _p(fg_idx.contiguous()), _p(fg_key.contiguous()), fg_idx.shape[1],
-                            _p(bg_idx.contiguous()), _p(bg_key.contiguous()), bg_idx.shape[1], int(n_s), _p(boxes.contiguous()),
-                            _p(cls), _p(argmax), B, R, _p(ob), _p(ov), _p(oc), _p(og), _p(counts)), "cr_roi_compact")
+    _lib.call("cr_roi_compact", fg_idx.contiguous(), fg_key.contiguous(), fg_idx.shape[1], bg_idx.contiguous(),
+              bg_key.contiguous(), bg_idx.shape[1], int(n_s), boxes.contiguous(), cls, argmax, B, R, ob, ov, oc, og, counts)
     return ob, ov.bool(), oc, og, counts
 
 
 class _BoxLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scores, deltas, valid, cls, pboxes, gt_idx, gt_boxes, weights, scale_clamp):
-        _p = _Args()
         B, S = valid.shape
         N, C = scores.shape
         K = C - 1
@@ -1941,11 +1801,9 @@ class _BoxLoss(torch.autograd.Function):
         ds = torch.empty((N, C), dtype=f32, device=dev)
         dd = torch.empty((N, K * 4), dtype=f32, device=dev)
         pred = torch.empty((N, 4), dtype=f32, device=dev)
-        lib = _lib.load()
-        _chk(lib.cr_box_loss(_ctx(scores), _p(scores.detach().float().contiguous()), _p(deltas.detach().float().contiguous()),
-                             _p(valid.to(torch.uint8).contiguous()), _p(cls.contiguous()), _p(pboxes.contiguous()),
-                             _p(gt_idx.contiguous()), _p(gt_boxes.contiguous()), B, S, gt_boxes.shape[1], K, _f4(weights),
-                             float(scale_clamp), _p(ws), _p(sums), _p(ds), _p(dd), _p(pred)), "cr_box_loss")
+        _lib.call("cr_box_loss", scores.detach().float().contiguous(), deltas.detach().float().contiguous(),
+                  valid.to(torch.uint8).contiguous(), cls.contiguous(), pboxes.contiguous(), gt_idx.contiguous(),
+                  gt_boxes.contiguous(), B, S, gt_boxes.shape[1], K, _f4(weights), float(scale_clamp), ws, sums, ds, dd, pred)
         ctx.save_for_backward(ds, dd)
         ctx.dt = (scores.dtype, deltas.dtype)
         ctx.set_materialize_grads(False)       # outputs nobody differentiates arrive as None, not as zero fills
@@ -1968,10 +1826,9 @@ def box_loss(scores, deltas, valid, cls, pboxes, gt_idx, gt_boxes, weights, scal
 # 3D head on the static-shape path: class gather + fused decode/loss + reductions
 # --------------------------------------------------------------------------
 CUBE_OFF = (0, 2, 3, 6, 15, 16, 20, 21, 24, 26, 27, 30)      # chunk starts of buf39 (x n), see include/cr3dod.h
-Z_TYPES = {"direct": 0, "sigmoid": 1, "log": 2}           # MODEL.ROI_CUBE_HEAD.Z_TYPE values the kernels decode (roi_heads.py:2404-2410)
-
-
-Z_TYPES["clusters"] = 3
+CUBE_DIM = (2, 1, 3, 9, 1, 4, 1, 3, 2, 1, 3, 9)
+# MODEL.ROI_CUBE_HEAD.Z_TYPE values the kernels decode (roi_heads.py:2404-2410)
+Z_TYPES = {"direct": 0, "sigmoid": 1, "log": 2, "clusters": 3}
 
 
 def z_type_code(z_type):
@@ -1990,11 +1847,54 @@ def z_config(z_type="direct", bins=1, z_scales=None, z_stats=None):
         raise ValueError("Z_TYPE 'clusters' needs CLUSTER_BINS > 1 and priors_z_stats")
     f = lambda t: None if t is None else t.detach().float().contiguous()
     return (code, bins, f(z_scales) if bins > 1 else None, f(z_stats) if code == 3 else None)
-CUBE_DIM = (2, 1, 3, 9, 1, 4, 1, 3, 2, 1, 3, 9)
 
 
 def _chunks(buf, n):
     return [buf[o * n:(o + d) * n] for o, d in zip(CUBE_OFF, CUBE_DIM)]
+
+
+def _cube_select(raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors, meta, boxes, zc, rows=39):
+    """forward plumbing of the two 3D-head loss Functions: cr_cube_select of raw (n,13K) into a fresh buffer of `rows` x n floats
+    whose first 39 rows are buf39 -> (raw32, the buffer, validf (n) uint8, clsc (n) int32, layout as c_int[5], boxes f32)"""
+    _need_cuda(raw, "cube head output")
+    B, S = cls.shape
+    n = B * kf
+    dev = raw.device
+    raw32 = raw.detach().float().contiguous()
+    buf = torch.empty((rows * n,), dtype=f32, device=dev)
+    validf = torch.empty((n,), dtype=torch.uint8, device=dev)
+    clsc = torch.empty((n,), dtype=torch.int32, device=dev)
+    lay = (_ct.c_int * 5)(*[int(v) for v in layout])
+    boxes = boxes.float().contiguous()
+    _lib.call("cr_cube_select", raw32, raw32.shape[1], lay, int(K), cls.contiguous(), valid.to(torch.uint8).contiguous(),
+              gt_idx.contiguous(), B, S, int(kf), gt3d.shape[1], gt3d.contiguous(), gtpose.contiguous(), priors,
+              meta.contiguous(), buf, validf, clsc, zc[0], zc[1], zc[2], zc[3], boxes)
+    return raw32, buf, validf, clsc, lay, boxes
+
+
+def _cube_loss_ins(buf, boxes, n):
+    """-> (chunks of buf39, the 13-pointer input array of the loss kernels: the chunks with the RoI boxes after the fifth)"""
+    ch = _chunks(buf, n)
+    ins = ch[:5] + [boxes] + ch[5:]
+    return ch, ctypes.cast((ctypes.c_void_p * 13)(*[t.data_ptr() for t in ins]), ctypes.c_void_p)
+
+
+def _cube_grads(n, dev, zraw=False):
+    """one buffer for what the loss backward kernels write, split: g_dxy, g_zr, g_dr, g_Ra, g_u (+ g_zraw)"""
+    cuts = (0, 2, 3, 6, 15, 16) + ((17,) if zraw else ())
+    g = torch.empty((cuts[-1] * n,), dtype=f32, device=dev)
+    return [g[a * n:b * n] for a, b in zip(cuts, cuts[1:])]
+
+
+def _cube_select_bwd(raw32, layout, K, B, kf, validf, clsc, grads, g_usel, zc, boxes):
+    """backward plumbing of the two 3D-head loss Functions: cr_cube_select_bwd of the five decoded-quantity gradients and the
+    selected uncertainty's -> (g_raw like raw32, layout as c_int[5])"""
+    g_dxy, g_zr, g_dr, g_Ra, g_u = grads
+    g_raw = torch.empty_like(raw32)
+    lay = (_ct.c_int * 5)(*layout)
+    _lib.call("cr_cube_select_bwd", raw32, raw32.shape[1], lay, K, B, kf, validf, clsc, g_dxy, g_zr, g_dr, g_Ra, g_u,
+              g_usel.contiguous(), g_raw, zc[0], zc[1], zc[2], zc[3], boxes)
+    return g_raw, lay
 
 
 class _CubeHeadLoss(torch.autograd.Function):
@@ -2002,30 +1902,13 @@ class _CubeHeadLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors, meta, boxes, flags):
-        _p = _Args()
-        _need_cuda(raw, "cube head output")
-        B, S = cls.shape
-        n = B * kf
-        dev = raw.device
-        raw32 = raw.detach().float().contiguous()
-        buf = torch.empty((39 * n,), dtype=f32, device=dev)
-        validf = torch.empty((n,), dtype=torch.uint8, device=dev)
-        clsc = torch.empty((n,), dtype=torch.int32, device=dev)
-        lay = (_ct.c_int * 5)(*[int(v) for v in layout])
-        lib = _lib.load()
-        boxes = boxes.float().contiguous()
-        _chk(lib.cr_cube_select(_ctx(raw), _p(raw32), raw32.shape[1], lay, int(K), _p(cls.contiguous()),
-                                _p(valid.to(torch.uint8).contiguous()), _p(gt_idx.contiguous()), B, S, int(kf), gt3d.shape[1],
-                                _p(gt3d.contiguous()), _p(gtpose.contiguous()), _p(priors), _p(meta.contiguous()), _p(buf),
-                                _p(validf), _p(clsc), flags[4][0], flags[4][1], _p(flags[4][2]), _p(flags[4][3]), _p(boxes)),
-             "cr_cube_select")
-        ch = _chunks(buf, n)
-        ins = ch[:5] + [boxes] + ch[5:]
-        arr = (ctypes.c_void_p * 13)(*[t.data_ptr() for t in ins])
-        losses = torch.empty((n, 5), dtype=f32, device=dev)
-        dec = torch.empty((n, 17), dtype=f32, device=dev)
-        _chk(lib.cr_cube_loss_fwd(_ctx(raw), ctypes.cast(arr, ctypes.c_void_p), n, *flags[:4], _p(losses), _p(dec)),
-             "cr_cube_loss_fwd")
+        B, n = cls.shape[0], cls.shape[0] * kf
+        raw32, buf, validf, clsc, _, boxes = _cube_select(raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors, meta, boxes,
+                                                          flags[4])
+        ch, arr = _cube_loss_ins(buf, boxes, n)
+        losses = torch.empty((n, 5), dtype=f32, device=raw.device)
+        dec = torch.empty((n, 17), dtype=f32, device=raw.device)
+        _lib.call("cr_cube_loss_fwd", arr, n, *flags[:4], losses, dec)
         ctx.keep = (raw32, buf, validf, clsc, boxes, tuple(layout), int(K), B, int(kf), flags, raw.dtype)
         ctx.set_materialize_grads(False)       # outputs nobody differentiates arrive as None, not as zero fills
         ctx.mark_non_differentiable(dec, buf, validf)
@@ -2033,23 +1916,12 @@ class _CubeHeadLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gl, g_usel, _gd, _gb, _gv):
-        _p = _Args()
         raw32, buf, validf, clsc, boxes, layout, K, B, kf, flags, dt = ctx.keep
         n = B * kf
-        dev = raw32.device
-        ch = _chunks(buf, n)
-        ins = ch[:5] + [boxes] + ch[5:]
-        arr = (ctypes.c_void_p * 13)(*[t.data_ptr() for t in ins])
-        g = torch.empty((16 * n,), dtype=f32, device=dev)
-        g_dxy, g_zr, g_dr, g_Ra, g_u = g[:2 * n], g[2 * n:3 * n], g[3 * n:6 * n], g[6 * n:15 * n], g[15 * n:]
-        lib = _lib.load()
-        _chk(lib.cr_cube_loss_bwd(_ctx(raw32), ctypes.cast(arr, ctypes.c_void_p), n, *flags[:4], _p(gl.contiguous()),
-                                  _p(g_dxy), _p(g_zr), _p(g_dr), _p(g_Ra), _p(g_u)), "cr_cube_loss_bwd")
-        g_raw = torch.empty_like(raw32)
-        lay = (_ct.c_int * 5)(*layout)
-        _chk(lib.cr_cube_select_bwd(_ctx(raw32), _p(raw32), raw32.shape[1], lay, K, B, kf, _p(validf), _p(clsc), _p(g_dxy),
-                                    _p(g_zr), _p(g_dr), _p(g_Ra), _p(g_u), _p(g_usel.contiguous()), _p(g_raw), flags[4][0], flags[4][1],
-                                    _p(flags[4][2]), _p(flags[4][3]), _p(boxes)), "cr_cube_select_bwd")
+        _, arr = _cube_loss_ins(buf, boxes, n)
+        grads = _cube_grads(n, raw32.device)
+        _lib.call("cr_cube_loss_bwd", arr, n, *flags[:4], gl.contiguous(), *grads)
+        g_raw, _ = _cube_select_bwd(raw32, layout, K, B, kf, validf, clsc, grads, g_usel, flags[4], boxes)
         return (g_raw.to(dt),) + (None,) * 12
 
 
@@ -2060,33 +1932,17 @@ class _CubeHeadLossNondis(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, meta, boxes, flags):
-        _p = _Args()
-        _need_cuda(raw, "cube head output")
-        B, S = cls.shape
-        n = B * kf
-        dev = raw.device
-        raw32 = raw.detach().float().contiguous()
-        buf42 = torch.empty((42 * n,), dtype=f32, device=dev)
-        buf, norm = buf42[:39 * n], buf42[39 * n:]
-        validf = torch.empty((n,), dtype=torch.uint8, device=dev)
-        clsc = torch.empty((n,), dtype=torch.int32, device=dev)
-        lay = (_ct.c_int * 5)(*[int(v) for v in layout])
-        lib = _lib.load()
-        boxes = boxes.float().contiguous()
+        B, n = cls.shape[0], cls.shape[0] * kf
         zc = flags[3]
-        _chk(lib.cr_cube_select(_ctx(raw), _p(raw32), raw32.shape[1], lay, int(K), _p(cls.contiguous()),
-                                _p(valid.to(torch.uint8).contiguous()), _p(gt_idx.contiguous()), B, S, int(kf), gt3d.shape[1],
-                                _p(gt3d.contiguous()), _p(gtpose.contiguous()), _p(None), _p(meta.contiguous()), _p(buf),
-                                _p(validf), _p(clsc), zc[0], zc[1], _p(zc[2]), _p(zc[3]), _p(boxes)), "cr_cube_select")
-        _chk(lib.cr_cube_select_norm(_ctx(raw), _p(raw32), raw32.shape[1], lay, int(K), B, int(kf), _p(clsc), zc[0], zc[1],
-                                     _p(zc[2]), _p(zc[3]), _p(boxes), _p(norm)), "cr_cube_select_norm")
-        ch = _chunks(buf, n)
-        ins = ch[:5] + [boxes] + ch[5:]
-        arr = (ctypes.c_void_p * 13)(*[t.data_ptr() for t in ins])
-        losses = torch.empty((n, 5), dtype=f32, device=dev)
-        dec = torch.empty((n, 17), dtype=f32, device=dev)
-        _chk(lib.cr_cube_nondis_fwd(_ctx(raw), ctypes.cast(arr, ctypes.c_void_p), _p(norm), n, *flags[:3], zc[0], _p(losses),
-                                    _p(dec)), "cr_cube_nondis_fwd")
+        raw32, buf42, validf, clsc, lay, boxes = _cube_select(raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, None, meta, boxes,
+                                                              zc, rows=42)
+        buf, norm = buf42[:39 * n], buf42[39 * n:]
+        _lib.call("cr_cube_select_norm", raw32, raw32.shape[1], lay, int(K), B, int(kf), clsc, zc[0], zc[1], zc[2], zc[3],
+                  boxes, norm)
+        ch, arr = _cube_loss_ins(buf, boxes, n)
+        losses = torch.empty((n, 5), dtype=f32, device=raw.device)
+        dec = torch.empty((n, 17), dtype=f32, device=raw.device)
+        _lib.call("cr_cube_nondis_fwd", arr, norm, n, *flags[:3], zc[0], losses, dec)
         ctx.keep = (raw32, buf42, validf, clsc, boxes, tuple(layout), int(K), B, int(kf), flags, raw.dtype)
         ctx.set_materialize_grads(False)       # outputs nobody differentiates arrive as None, not as zero fills
         ctx.mark_non_differentiable(dec, buf, validf)
@@ -2094,29 +1950,17 @@ class _CubeHeadLossNondis(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gl, g_usel, _gd, _gb, _gv):
-        _p = _Args()
         raw32, buf42, validf, clsc, boxes, layout, K, B, kf, flags, dt = ctx.keep
         n = B * kf
-        dev = raw32.device
         buf, norm = buf42[:39 * n], buf42[39 * n:]
-        ch = _chunks(buf, n)
-        ins = ch[:5] + [boxes] + ch[5:]
-        arr = (ctypes.c_void_p * 13)(*[t.data_ptr() for t in ins])
-        g = torch.empty((17 * n,), dtype=f32, device=dev)
-        g_dxy, g_zr, g_dr, g_Ra, g_u, g_zraw = g[:2 * n], g[2 * n:3 * n], g[3 * n:6 * n], g[6 * n:15 * n], g[15 * n:16 * n], g[16 * n:]
-        lib = _lib.load()
+        _, arr = _cube_loss_ins(buf, boxes, n)
+        *grads, g_zraw = _cube_grads(n, raw32.device, zraw=True)
         zc = flags[3]
-        _chk(lib.cr_cube_nondis_bwd(_ctx(raw32), ctypes.cast(arr, ctypes.c_void_p), _p(norm), n, *flags[:3], zc[0],
-                                    _p(gl.contiguous()), _p(g_dxy), _p(g_zr), _p(g_dr), _p(g_Ra), _p(g_u), _p(g_zraw)),
-             "cr_cube_nondis_bwd")
-        g_raw = torch.empty_like(raw32)
-        lay = (_ct.c_int * 5)(*layout)
-        _chk(lib.cr_cube_select_bwd(_ctx(raw32), _p(raw32), raw32.shape[1], lay, K, B, kf, _p(validf), _p(clsc), _p(g_dxy),
-                                    _p(g_zr), _p(g_dr), _p(g_Ra), _p(g_u), _p(g_usel.contiguous()), _p(g_raw), zc[0], zc[1],
-                                    _p(zc[2]), _p(zc[3]), _p(boxes)), "cr_cube_select_bwd")
+        _lib.call("cr_cube_nondis_bwd", arr, norm, n, *flags[:3], zc[0], gl.contiguous(), *grads, g_zraw)
+        g_raw, lay = _cube_select_bwd(raw32, layout, K, B, kf, validf, clsc, grads, g_usel, zc, boxes)
         if zc[0] != 0:                         # 'direct' has no normalised depth space: its z term went through g_zr
-            _chk(lib.cr_cube_select_bwd_zraw(_ctx(raw32), raw32.shape[1], lay, K, B, kf, _p(validf), _p(clsc), _p(g_zraw),
-                                             _p(g_raw), zc[1], _p(zc[2]), _p(boxes)), "cr_cube_select_bwd_zraw")
+            _lib.call("cr_cube_select_bwd_zraw", raw32.shape[1], lay, K, B, kf, validf, clsc, g_zraw, g_raw, zc[1], zc[2],
+                      boxes)
         return (g_raw.to(dt),) + (None,) * 11
 
 
@@ -2141,32 +1985,27 @@ def cube_head_loss(raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors,
 
 def cube_decode_infer(raw, layout, K, cls, img, boxes, meta6, priors, allocentric=True, z_type="direct", z_cfg=None):
     """inference decode of the 3D head (no autograd) -> (n,42), see cr_cube_decode_infer."""
-    _p = _Args()
     _need_cuda(raw, "cube head output")
     n = raw.shape[0]
     out = torch.empty((n, 42), dtype=f32, device=raw.device)
     raw32 = raw.detach().float().contiguous()
     lay = (_ct.c_int * 5)(*[int(v) for v in layout])
-    lib = _lib.load()
     zc = z_cfg or z_config(z_type)
-    _chk(lib.cr_cube_decode_infer(_ctx(raw), _p(raw32), raw32.shape[1], lay, int(K), _p(cls.contiguous()),
-                                  _p(img.to(torch.int32).contiguous()), _p(boxes.float().contiguous()), _p(meta6.contiguous()),
-                                  _p(priors), n, int(bool(allocentric)), _p(out), zc[0], zc[1], _p(zc[2]), _p(zc[3])), "cr_cube_decode_infer")
+    _lib.call("cr_cube_decode_infer", raw32, raw32.shape[1], lay, int(K), cls.contiguous(), img.to(torch.int32).contiguous(),
+              boxes.float().contiguous(), meta6.contiguous(), priors, n, int(bool(allocentric)), out, zc[0], zc[1], zc[2],
+              zc[3])
     return out
 
 
 class _CubeReduce(torch.autograd.Function):
     @staticmethod
     def forward(ctx, L, u_sel, buf, dec, validf, inverse_z):
-        _p = _Args()
         n = L.shape[0]
         dev = L.device
         out = torch.empty((16,), dtype=f32, device=dev)
         red, cnt, stats = out[:6], out[6:12], out[12:]
-        lib = _lib.load()
         Lc = L.detach().contiguous()
-        _chk(lib.cr_cube_reduce(_ctx(L), _p(Lc), _p(buf), _p(dec), _p(validf), n, int(inverse_z), _p(red), _p(cnt),
-                                _p(stats)), "cr_cube_reduce")
+        _lib.call("cr_cube_reduce", Lc, buf, dec, validf, n, int(inverse_z), red, cnt, stats)
         ctx.keep = (Lc, buf, validf, cnt, int(inverse_z))
         ctx.set_materialize_grads(False)       # outputs nobody differentiates arrive as None, not as zero fills
         ctx.mark_non_differentiable(stats)
@@ -2174,14 +2013,11 @@ class _CubeReduce(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gred, _gs):
-        _p = _Args()
         Lc, buf, validf, cnt, inverse_z = ctx.keep
         n = Lc.shape[0]
         gL = torch.empty_like(Lc)
         gu = torch.empty((n,), dtype=f32, device=Lc.device)
-        lib = _lib.load()
-        _chk(lib.cr_cube_reduce_bwd(_ctx(Lc), _p(Lc), _p(buf), _p(validf), n, inverse_z, _p(cnt), _p(gred.contiguous()),
-                                    _p(gL), _p(gu)), "cr_cube_reduce_bwd")
+        _lib.call("cr_cube_reduce_bwd", Lc, buf, validf, n, inverse_z, cnt, gred.contiguous(), gL, gu)
         return gL, gu, None, None, None, None
 
 
@@ -2205,12 +2041,10 @@ class _WeakCubeLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, raw, layout, K, cls, valid, gt_idx, kf, gt_boxes, gt3d, gtpose, prior_mean, prior_std, meta, table, normals,
                 boxes, depth, terms, pgz_mode, weights, allocentric, zt):
-        _p = _Args()
         _need_cuda(raw, "cube head output")
         B, S = cls.shape
         n, G = B * kf, gt3d.shape[1]
         dev = raw.device
-        lib = _lib.load()
         raw32 = raw.detach().float().contiguous()
         buf = torch.empty((39 * n,), dtype=f32, device=dev)
         validf = torch.empty((n,), dtype=torch.uint8, device=dev)
@@ -2218,9 +2052,9 @@ class _WeakCubeLoss(torch.autograd.Function):
         lay = (_ct.c_int * 5)(*[int(v) for v in layout])
         cls, gt_idx, gt_boxes, table = cls.contiguous(), gt_idx.contiguous(), gt_boxes.float().contiguous(), table.contiguous()
         boxes = boxes.float().contiguous()
-        _chk(lib.cr_cube_select(_ctx(raw), _p(raw32), raw32.shape[1], lay, int(K), _p(cls), _p(valid.to(torch.uint8).contiguous()),
-                                _p(gt_idx), B, S, int(kf), G, _p(gt3d.contiguous()), _p(gtpose.contiguous()), _p(prior_mean),
-                                _p(meta.contiguous()), _p(buf), _p(validf), _p(clsc), zt[0], zt[1], _p(zt[2]), _p(zt[3]), _p(boxes)), "cr_cube_select")
+        _lib.call("cr_cube_select", raw32, raw32.shape[1], lay, int(K), cls, valid.to(torch.uint8).contiguous(), gt_idx, B, S,
+                  int(kf), G, gt3d.contiguous(), gtpose.contiguous(), prior_mean, meta.contiguous(), buf, validf, clsc, zt[0],
+                  zt[1], zt[2], zt[3], boxes)
         ch = _chunks(buf, n)
         ins = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in (ch[0], ch[1], ch[2], ch[3], ch[4], ch[6], ch[7], boxes)])
         out = torch.empty((n * (8 + 17 + 4 + 1 + 1) + 2 * B + 27,), dtype=f32, device=dev)
@@ -2233,9 +2067,8 @@ class _WeakCubeLoss(torch.autograd.Function):
         Lraw, dec, pbox, ztgt, med, pimg = take(8 * n), take(17 * n), take(4 * n), take(n), take(n), take(2 * B)
         red, cnt, stats, aux = take(9), take(9), take(8), take(1)
         ibox = torch.empty((n, 4), dtype=torch.int32, device=dev)
-        common = (_ctx(raw), ctypes.cast(ins, ctypes.c_void_p), _p(validf), _p(clsc), _p(gt_idx), _p(gt_boxes), _p(prior_std), _p(table),
-                  _p(normals), B, int(kf), S, G, int(bool(allocentric)), int(terms))
-        _chk(lib.cr_weak_loss_fwd(*common, _p(Lraw), _p(dec), _p(pbox), _p(ibox), _p(pimg)), "cr_weak_loss_fwd")
+        _lib.call("cr_weak_loss_fwd", ctypes.cast(ins, ctypes.c_void_p), validf, clsc, gt_idx, gt_boxes, prior_std, table, normals, B,
+                  int(kf), S, G, int(bool(allocentric)), int(terms), Lraw, dec, pbox, ibox, pimg)
         H = W = 0
         if pgz_mode:
             depth = depth.float().contiguous()
@@ -2244,13 +2077,12 @@ class _WeakCubeLoss(torch.autograd.Function):
             img = _WEAK_IMG.get((B, kf, str(dev)))
             if img is None:
                 img = _WEAK_IMG[(B, kf, str(dev))] = (torch.arange(n, device=dev) // kf).to(torch.int32)
-            _chk(lib.cr_box_median(_ctx(raw), _p(depth), B, H, W, _p(ibox), _p(img), n, _p(med)), "cr_box_median")
+            _lib.call("cr_box_median", depth, B, H, W, ibox, img, n, med)
         rin = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in (ch[4], ch[8], ch[9], ch[10])])
         wts = (_ct.c_float * 9)(*[float(w) for w in weights])
-        _chk(lib.cr_weak_loss_reduce(_ctx(raw), ctypes.cast(rin, ctypes.c_void_p), _p(validf), _p(table), _p(depth if pgz_mode else None),
-                                     H, W, _p(med if pgz_mode == 1 else None), _p(gt_boxes), _p(gt_idx), B, int(kf), S, G, int(terms),
-                                     int(pgz_mode), wts, _p(Lraw), _p(dec), _p(pbox), _p(ibox), _p(pimg), _p(ztgt), _p(red), _p(cnt),
-                                     _p(stats), _p(aux)), "cr_weak_loss_reduce")
+        _lib.call("cr_weak_loss_reduce", ctypes.cast(rin, ctypes.c_void_p), validf, table, depth if pgz_mode else None, H, W,
+                  med if pgz_mode == 1 else None, gt_boxes, gt_idx, B, int(kf), S, G, int(terms), int(pgz_mode), wts, Lraw, dec,
+                  pbox, ibox, pimg, ztgt, red, cnt, stats, aux)
         ctx.keep = (raw32, buf, validf, clsc, boxes, tuple(layout), int(K), B, int(kf), S, G, raw.dtype, cls, gt_idx, gt_boxes, prior_std,
                     table, normals, int(bool(allocentric)), int(terms), out, zt)
         dec2, pbox2 = dec.view(n, 17), pbox.view(n, 4)
@@ -2260,12 +2092,10 @@ class _WeakCubeLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gred, *_unused):
-        _p = _Args()
         (raw32, buf, validf, clsc, boxes, layout, K, B, kf, S, G, dt, cls, gt_idx, gt_boxes, prior_std, table, normals, allocentric, terms,
          out, zt) = ctx.keep
         n = B * kf
         dev = raw32.device
-        lib = _lib.load()
         ch = _chunks(buf, n)
         ins = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in (ch[0], ch[1], ch[2], ch[3], ch[4], ch[6], ch[7], boxes)])
         Lraw, dec, ztgt, pimg = out[:8 * n], out[8 * n:25 * n], out[29 * n:30 * n], out[31 * n:31 * n + 2 * B]
@@ -2274,14 +2104,13 @@ class _WeakCubeLoss(torch.autograd.Function):
         g = torch.empty((17 * n,), dtype=f32, device=dev)
         g_dxy, g_zr, g_dr, g_Ra, g_u, zero = g[:2 * n], g[2 * n:3 * n], g[3 * n:6 * n], g[6 * n:15 * n], g[15 * n:16 * n], g[16 * n:]
         zero.zero_()
-        _chk(lib.cr_weak_loss_bwd(_ctx(raw32), ctypes.cast(ins, ctypes.c_void_p), _p(validf), _p(clsc), _p(gt_idx), _p(gt_boxes),
-                                  _p(prior_std), _p(table), _p(normals), B, kf, S, G, allocentric, terms, _p(gred.float().contiguous()),
-                                  _p(cnt), _p(aux), _p(Lraw), _p(dec), _p(ztgt), _p(pimg), _p(g_dxy), _p(g_zr), _p(g_dr), _p(g_Ra),
-                                  _p(g_u)), "cr_weak_loss_bwd")
+        _lib.call("cr_weak_loss_bwd", ctypes.cast(ins, ctypes.c_void_p), validf, clsc, gt_idx, gt_boxes, prior_std, table,
+                  normals, B, kf, S, G, allocentric, terms, gred.float().contiguous(), cnt, aux, Lraw, dec, ztgt, pimg, g_dxy,
+                  g_zr, g_dr, g_Ra, g_u)
         g_raw = torch.empty_like(raw32)
         lay = (_ct.c_int * 5)(*layout)
-        _chk(lib.cr_cube_select_bwd(_ctx(raw32), _p(raw32), raw32.shape[1], lay, K, B, kf, _p(validf), _p(clsc), _p(g_dxy), _p(g_zr),
-                                    _p(g_dr), _p(g_Ra), _p(g_u), _p(zero), _p(g_raw), zt[0], zt[1], _p(zt[2]), _p(zt[3]), _p(boxes)), "cr_cube_select_bwd")
+        _lib.call("cr_cube_select_bwd", raw32, raw32.shape[1], lay, K, B, kf, validf, clsc, g_dxy, g_zr, g_dr, g_Ra, g_u, zero,
+                  g_raw, zt[0], zt[1], zt[2], zt[3], boxes)
         return (g_raw.to(dt),) + (None,) * 21
 
 
@@ -2305,7 +2134,6 @@ def weak_cube_loss(raw, layout, K, cls, valid, gt_idx, kf, gt_boxes, gt3d, gtpos
 class _RPNUnpack(torch.autograd.Function):
     @staticmethod
     def forward(ctx, A, *ys):
-        _p = _Args()
         L, B, C = len(ys), ys[0].shape[0], ys[0].shape[-1]
         ys = [y.contiguous() for y in ys]
         cells = [y.numel() // (B * C) for y in ys]
@@ -2315,9 +2143,7 @@ class _RPNUnpack(torch.autograd.Function):
         deltas = torch.empty((B, atot, 4), dtype=f32, device=dev)
         padded = torch.empty((B, L, amax), dtype=f32, device=dev)
         yp, ca = (_ct.c_void_p * L)(*[y.data_ptr() for y in ys]), (_ct.c_int * L)(*cells)
-        _p.keep.extend(ys)
-        _chk(_lib.load().cr_rpn_unpack(_ctx(ys[0]), yp, ca, L, B, A, C, _lib.ptr(logits), _lib.ptr(deltas), _lib.ptr(padded)),
-             "cr_rpn_unpack")
+        _lib.call("cr_rpn_unpack", yp, ca, L, B, A, C, logits, deltas, padded)
         ctx.cfg = (A, C, B, cells, [tuple(y.shape) for y in ys])
         ctx.set_materialize_grads(False)       # outputs nobody differentiates arrive as None, not as zero fills
         ctx.mark_non_differentiable(padded)
@@ -2325,7 +2151,6 @@ class _RPNUnpack(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits, ddeltas, _dpad):
-        _p = _Args()
         A, C, B, cells, shapes = ctx.cfg
         L = len(cells)
         ref = dlogits if dlogits is not None else ddeltas
@@ -2333,7 +2158,7 @@ class _RPNUnpack(torch.autograd.Function):
         dl = None if dlogits is None else dlogits.contiguous()
         dd = None if ddeltas is None else ddeltas.contiguous()
         dp, ca = (_ct.c_void_p * L)(*[d.data_ptr() for d in dys]), (_ct.c_int * L)(*cells)
-        _chk(_lib.load().cr_rpn_pack_grad(_ctx(ref), _p(dl), _p(dd), dp, ca, L, B, A, C), "cr_rpn_pack_grad")
+        _lib.call("cr_rpn_pack_grad", dl, dd, dp, ca, L, B, A, C)
         return (None,) + tuple(dys)
 
 
@@ -2343,7 +2168,6 @@ class _RPNUnpackStacked(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, A, cells, B, Y):
-        _p = _Args()
         Y = Y.contiguous()
         L, C = len(cells), Y.shape[-1]
         assert Y.numel() == B * sum(cells) * C, "stacked RPN output does not match the level sizes"
@@ -2356,9 +2180,7 @@ class _RPNUnpackStacked(torch.autograd.Function):
         for c in cells:
             offs.append(offs[-1] + B * c * C * 4)
         yp, ca = (_ct.c_void_p * L)(*[Y.data_ptr() + o for o in offs[:-1]]), (_ct.c_int * L)(*cells)
-        _p.keep.append(Y)
-        _chk(_lib.load().cr_rpn_unpack(_ctx(Y), yp, ca, L, B, A, C, _lib.ptr(logits), _lib.ptr(deltas), _lib.ptr(padded)),
-             "cr_rpn_unpack")
+        _lib.call("cr_rpn_unpack", yp, ca, L, B, A, C, logits, deltas, padded)
         ctx.cfg = (A, C, B, tuple(cells), tuple(Y.shape), offs)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(padded)
@@ -2366,7 +2188,6 @@ class _RPNUnpackStacked(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits, ddeltas, _dpad):
-        _p = _Args()
         A, C, B, cells, shape, offs = ctx.cfg
         L = len(cells)
         ref = dlogits if dlogits is not None else ddeltas
@@ -2374,7 +2195,7 @@ class _RPNUnpackStacked(torch.autograd.Function):
         dl = None if dlogits is None else dlogits.contiguous()
         dd = None if ddeltas is None else ddeltas.contiguous()
         dp, ca = (_ct.c_void_p * L)(*[dY.data_ptr() + o for o in offs[:-1]]), (_ct.c_int * L)(*cells)
-        _chk(_lib.load().cr_rpn_pack_grad(_ctx(ref), _p(dl), _p(dd), dp, ca, L, B, A, C), "cr_rpn_pack_grad")
+        _lib.call("cr_rpn_pack_grad", dl, dd, dp, ca, L, B, A, C)
         return None, None, None, dY
 
 
@@ -2410,20 +2231,17 @@ def gt_pack(gt_instances, G, boxes, classes, boxes3D, poses):
         has3 = n and g.has("gt_boxes3D")
         b3[i] = dev(g.gt_boxes3D, f32) if has3 else None
         pp[i] = dev(g.gt_poses, f32) if has3 else None
-    _chk(_lib.load().cr_gt_pack(_ctx(boxes), bp, cp, b3, pp, cnt, B, int(G), _lib.ptr(boxes), _lib.ptr(classes), _lib.ptr(boxes3D),
-                                _lib.ptr(poses)), "cr_gt_pack")
+    _lib.call("cr_gt_pack", bp, cp, b3, pp, cnt, B, int(G), boxes, classes, boxes3D, poses)
 
 
 def topk(x, k):
     """row-wise top-k of a 2-D float32 tensor: (values sorted descending, int64 indices), ties -> lower index first;
     own radix-select + bitonic merge (csrc/topk.hip: two launches, no memset nodes).  Shapes outside the kernel's range
     (k > 2048, too many candidates) fall back to torch.topk."""
-    _p = _Args()
     _need_cuda(x, "topk input")
     assert x.dim() == 2 and x.dtype == f32
     rows, n = x.shape
-    lib = _lib.load()
-    nb = lib.cr_topk_blocks(n, k) if k >= 1 else 0
+    nb = _lib.topk_blocks(n, k) if k >= 1 else 0
     if k < 1 or k > 2048 or k > n or nb * k > 16384:
         if torch.cuda.is_current_stream_capturing():
             # torch.topk's multi-block path zeroes its counters with hipMemsetAsync = memset NODES in the captured graph,
@@ -2436,68 +2254,55 @@ def topk(x, k):
     ws = torch.empty((rows * nb * k,), dtype=torch.int64, device=x.device)
     vals = torch.empty((rows, k), dtype=f32, device=x.device)
     idx = torch.empty((rows, k), dtype=torch.int64, device=x.device)
-    _chk(lib.cr_topk(_ctx(x), _p(xc), rows, n, k, _p(ws), _p(vals), _p(idx)), "cr_topk")
+    _lib.call("cr_topk", xc, rows, n, k, ws, vals, idx)
     return vals, idx
 
 
 def loss_guard(vals, scale, red, total, recent, stabilize, tolerance, gamma, flag):
     """divergence guard of train_net.py:202-220 in one launch (see include/cr3dod.h); all tensors on the device, in place"""
-    _p = _Args()
-    _chk(_lib.load().cr_loss_guard(_ctx(vals), _p(vals), vals.numel(), float(scale), _p(red), _p(total), _p(recent),
-                                   int(bool(stabilize)), float(tolerance), float(gamma), _p(flag)), "cr_loss_guard")
+    _lib.call("cr_loss_guard", vals, vals.numel(), float(scale), red, total, recent, int(bool(stabilize)), float(tolerance),
+              float(gamma), flag)
 
 
 def step_counters(flag, explode, success):
-    _p = _Args()
-    _chk(_lib.load().cr_step_counters(_ctx(flag), _p(flag), _p(explode), _p(success)), "cr_step_counters")
+    _lib.call("cr_step_counters", flag, explode, success)
 
 
 def nonfinite_flag(flat_grad, flag):
-    _p = _Args()
-    lib = _lib.load()
-    _chk(lib.cr_nonfinite_flag(_ctx(flat_grad), _p(flat_grad), flat_grad.numel(), _p(flag)), "cr_nonfinite_flag")
+    _lib.call("cr_nonfinite_flag", flat_grad, flat_grad.numel(), flag)
 
 
 def sgd_step(p, g, m, lr, momentum, weight_decay, grad_scale=1.0, skip_flag=None, lr_scale_dev=None, nesterov=False):
     """lr_scale_dev: optional device float; the step uses lr * lr_scale_dev[0] (read on the device -> graph-capturable)"""
-    _p = _Args()
-    lib = _lib.load()
-    fn = lib.cr_sgd_step_nesterov if nesterov else lib.cr_sgd_step
-    _chk(fn(_ctx(p), _p(p), _p(g), _p(m), p.numel(), float(lr), _p(lr_scale_dev), float(momentum),
-            float(weight_decay), float(grad_scale), _p(skip_flag)), "cr_sgd_step")
+    _lib.call("cr_sgd_step_nesterov" if nesterov else "cr_sgd_step", p, g, m, p.numel(), float(lr), lr_scale_dev, float(momentum),
+              float(weight_decay), float(grad_scale), skip_flag)
 
 
 def grad_clip_value(g, clip_value, grad_scale=1.0):
     """SOLVER.CLIP_GRADIENTS, CLIP_TYPE 'value': g = clamp(g * grad_scale, -clip_value, clip_value) in place"""
-    _p = _Args()
-    _chk(_lib.load().cr_grad_clip_value(_ctx(g), _p(g), g.numel(), float(clip_value), float(grad_scale)), "cr_grad_clip_value")
+    _lib.call("cr_grad_clip_value", g, g.numel(), float(clip_value), float(grad_scale))
 
 
 def grad_clip_norm(g, starts, counts, max_norm, norm_type=2.0, grad_scale=1.0, partial=None):
     """CLIP_TYPE 'norm': every parameter (starts[i], counts[i] inside the flat gradient g) scaled on its own by
     min(1, max_norm / (||g_i * grad_scale|| + 1e-6)), grad_scale folded in; partial: (len(starts) * 16,) float scratch"""
-    _p = _Args()
     n = int(starts.numel())
     if partial is None:
         partial = torch.empty(n * 16, dtype=torch.float32, device=g.device)
-    _chk(_lib.load().cr_grad_clip_norm(_ctx(g), _p(g), _p(starts), _p(counts), n, float(max_norm), float(norm_type),
-                                       float(grad_scale), _p(partial)), "cr_grad_clip_norm")
+    _lib.call("cr_grad_clip_norm", g, starts, counts, n, float(max_norm), float(norm_type), float(grad_scale), partial)
 
 
 def adam_tick(step, skip_flag=None):
     """advance the device-side count of applied Adam updates unless the step is skipped (cr_adam_tick)"""
-    _p = _Args()
-    _chk(_lib.load().cr_adam_tick(_ctx(step), _p(step), _p(skip_flag)), "cr_adam_tick")
+    _lib.call("cr_adam_tick", step, skip_flag)
 
 
 def adam_step(p, g, exp_avg, exp_avg_sq, max_exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, skip_flag=None,
               lr_scale_dev=None, decoupled=False):
     """torch.optim.Adam (decoupled=False) / AdamW (True) on one hyper-parameter segment of the flat buffers; max_exp_avg_sq:
     the amsgrad state or None; step: device float advanced by adam_tick"""
-    _p = _Args()
-    _chk(_lib.load().cr_adam_step(_ctx(p), _p(p), _p(g), _p(exp_avg), _p(exp_avg_sq), _p(max_exp_avg_sq), p.numel(), float(lr),
-                                  _p(lr_scale_dev), float(beta1), float(beta2), float(eps), float(weight_decay), float(grad_scale),
-                                  int(bool(decoupled)), _p(step), _p(skip_flag)), "cr_adam_step")
+    _lib.call("cr_adam_step", p, g, exp_avg, exp_avg_sq, max_exp_avg_sq, p.numel(), float(lr), lr_scale_dev, float(beta1),
+              float(beta2), float(eps), float(weight_decay), float(grad_scale), int(bool(decoupled)), step, skip_flag)
 
 
 # --------------------------------------------------------------------------
@@ -2505,64 +2310,56 @@ def adam_step(p, g, exp_avg, exp_avg_sq, max_exp_avg_sq, lr, beta1, beta2, eps, 
 # --------------------------------------------------------------------------
 def attention(qkv, B, N, H, D, scale):
     """qkv (B*N, 3*H*D) bf16 = output of the qkv linear -> (B*N, H*D) bf16 (cr_attention_fwd)."""
-    _p = _Args()
     _need_cuda(qkv, "attention input")
     assert qkv.dtype == bf16 and qkv.is_contiguous() and qkv.shape == (B * N, 3 * H * D)
     out = torch.empty((B * N, H * D), dtype=bf16, device=qkv.device)
-    _chk(_lib.load().cr_attention_fwd(_ctx(qkv), _p(qkv), _p(out), B, N, H, D, float(scale)), "cr_attention_fwd")
+    _lib.call("cr_attention_fwd", qkv, out, B, N, H, D, float(scale))
     return out
 
 
 def layernorm(x, gamma, beta, eps):
-    _p = _Args()
     _need_cuda(x, "layernorm input")
     assert x.dtype == bf16 and x.is_contiguous() and x.dim() == 2
     y = torch.empty_like(x)
-    _chk(_lib.load().cr_layernorm(_ctx(x), _p(x), _p(gamma.detach().float().contiguous()),
-                                  _p(beta.detach().float().contiguous()), _p(y), x.shape[0], x.shape[1], float(eps)),
-         "cr_layernorm")
+    _lib.call("cr_layernorm", x, gamma.detach().float().contiguous(), beta.detach().float().contiguous(), y, x.shape[0],
+              x.shape[1], float(eps))
     return y
 
 
 def gelu_(x):
-    _p = _Args()
     _need_cuda(x, "gelu input")
     assert x.dtype == bf16 and x.is_contiguous()
-    _chk(_lib.load().cr_gelu_inplace(_ctx(x), _p(x), x.numel()), "cr_gelu_inplace")
+    _lib.call("cr_gelu_inplace", x, x.numel())
     return x
 
 
 def scale_residual(x, y, gamma=None):
     """x + gamma * y on (M,C) bf16"""
-    _p = _Args()
     _need_cuda(x, "residual input")
     assert x.dtype == bf16 and y.dtype == bf16 and x.is_contiguous() and y.is_contiguous() and x.shape == y.shape
     out = torch.empty_like(x)
     g = gamma.detach().float().contiguous() if gamma is not None else None
-    _chk(_lib.load().cr_scale_residual(_ctx(x), _p(x), _p(y), _p(g), _p(out), x.shape[0], x.shape[1]), "cr_scale_residual")
+    _lib.call("cr_scale_residual", x, y, g, out, x.shape[0], x.shape[1])
     return out
 
 
 def scale_residual_layernorm(x, y, ls, gamma, beta, eps):
     """(x + ls * y, LayerNorm(x + ls * y)) on (M,C) bf16 in one kernel"""
-    _p = _Args()
     _need_cuda(x, "residual input")
     assert x.dtype == bf16 and y.dtype == bf16 and x.is_contiguous() and y.is_contiguous() and x.shape == y.shape
     xo, ho = torch.empty_like(x), torch.empty_like(x)
     l = ls.detach().float().contiguous() if ls is not None else None
-    _chk(_lib.load().cr_scale_residual_layernorm(_ctx(x), _p(x), _p(y), _p(l), _p(gamma.detach().float().contiguous()),
-                                                 _p(beta.detach().float().contiguous()), _p(xo), _p(ho), x.shape[0],
-                                                 x.shape[1], float(eps)), "cr_scale_residual_layernorm")
+    _lib.call("cr_scale_residual_layernorm", x, y, l, gamma.detach().float().contiguous(), beta.detach().float().contiguous(),
+              xo, ho, x.shape[0], x.shape[1], float(eps))
     return xo, ho
 
 
 def resize_bilinear_ac(x, size):
     """F.interpolate(..., mode='bilinear', align_corners=True) on NHWC bf16"""
-    _p = _Args()
     _need_cuda(x, "resize input")
     assert x.dtype == bf16 and x.is_contiguous() and x.dim() == 4
     B, h, w, C = x.shape
     Ho, Wo = int(size[0]), int(size[1])
     y = torch.empty((B, Ho, Wo, C), dtype=bf16, device=x.device)
-    _chk(_lib.load().cr_resize_bilinear_ac(_ctx(x), _p(x), _p(y), B, h, w, Ho, Wo, C), "cr_resize_bilinear_ac")
+    _lib.call("cr_resize_bilinear_ac", x, y, B, h, w, Ho, Wo, C)
     return y

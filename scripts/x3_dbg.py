@@ -8,7 +8,7 @@ w[1, :4] = torch.tensor([3.0e-38, 1.1754944e-38, 2.0 ** 100, -(2.0 ** -100)])
 w[2, :3] = torch.tensor([16777215.0, 1.0 + 2.0 ** -23, 1.0 - 2.0 ** -24])
 wd = w.cuda()
 out = torch.empty(rows * K * 3, dtype=torch.bfloat16, device="cuda")
-_lib.check(_lib.load().cr_weight_split3(_lib.ctx_for(wd.device), _lib.ptr(wd), _lib.ptr(out), rows, K), "x")
+_lib.call("cr_weight_split3", wd, out, rows, K)
 torch.cuda.synchronize()
 pl = out.view(rows, K // 32, 3, 4, 8).double().cpu()
 total = pl.sum(2)

@@ -45,7 +45,7 @@ def test_weight_split3_exact_and_layout():
     w[2, :3] = torch.tensor([16777215.0, 1.0 + 2.0 ** -23, 1.0 - 2.0 ** -24])                         # all 24 bits set
     wd = w.to(DEV)
     out = torch.empty(rows * K * 3, dtype=bf16, device=DEV)
-    _lib.check(_lib.load().cr_weight_split3(_lib.ctx_for(wd.device), _lib.ptr(wd), _lib.ptr(out), rows, K), "cr_weight_split3")
+    _lib.call("cr_weight_split3", wd, out, rows, K)
     torch.cuda.synchronize()
     pl = out.view(rows, K // 32, 3, 4, 8).double().cpu()              # [row][kb][plane][chunk c][e]
     total = pl.sum(2)                                                  # h + m + l, exact in f64

@@ -374,7 +374,7 @@ def test_two_segment_backward_equals_single_graph(built):
 def test_whole_step_graph_run_ahead_lr_schedule_and_gt_overflow():
     """GraphedTrainStep with the host running ahead of the device (the default: no per-step sync) at the bench's batch
     size -- the mode that faulted in round 1 (garbage sampling indices from aliased `.contiguous()` temporaries whose
-    pointers were read inline; every wrapper now owns its temporaries until the launch, hipops._Args).  Also: the
+    pointers were read inline; every kernel call now owns its arguments until the launch, _lib.call).  Also: the
     learning-rate schedule reaches the captured update through a device scalar (lr_scale = 0 freezes the parameters),
     cached compute copies of the weights follow the graph's updates, and a batch with more ground-truth rows than the
     captured buffers hold re-captures instead of failing."""

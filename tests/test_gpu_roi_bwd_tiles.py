@@ -32,7 +32,6 @@ def _rois(n_img, R, size, g, clustered=True):
 
 def _run(kind, shapes, rois, dout, C, grads=None):
     """kind: 'tiles' | 'atomic'; returns the list of gradient maps (NHWC f32)"""
-    lib = lib_mod.load()
     n = len(shapes)
     if grads is None:
         grads = [(torch.full if kind == "tiles" else torch.zeros)(s, *((7.0,) if kind == "tiles" else ()), dtype=f32, device=DEV)
@@ -42,14 +41,12 @@ def _run(kind, shapes, rois, dout, C, grads=None):
     Ws = (ctypes.c_int * n)(*[s[2] for s in shapes])
     sc = (ctypes.c_float * n)(*SCALES[:n])
     cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
-    ctx = lib_mod.ctx_for(DEV)
     af = 1 if dout.dtype == f32 else 0
     if kind == "tiles":
-        lib_mod.check(lib.cr_roi_align_bwd_set(ctx, cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, shapes[0][0], lib_mod.ptr(rois),
-                                               rois.shape[0], 7, 7, lib_mod.ptr(dout), af), "cr_roi_align_bwd_set")
+        lib_mod.call("cr_roi_align_bwd_set", cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, shapes[0][0], rois, rois.shape[0], 7, 7,
+                     dout, af)
     else:
-        lib_mod.check(lib.cr_roi_align_bwd(ctx, cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, lib_mod.ptr(rois), rois.shape[0],
-                                           7, 7, lib_mod.ptr(dout), af), "cr_roi_align_bwd")
+        lib_mod.call("cr_roi_align_bwd", cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, rois, rois.shape[0], 7, 7, dout, af)
     torch.cuda.synchronize()
     return grads
 

@@ -2020,7 +2020,15 @@ __global__ __launch_bounds__(CONV_T * KG) void k_conv_wgrad(WgP p) {
 // pixels (4 MFMA k-steps); KU = 2 sub-steps per stage.  MFMA-bound (1/16 of the bf16 rate): the f32 atomics of the
 // split-over-pixels scheme are hidden behind 16x more matrix time than in the bf16 kernel.
 // ---------------------------------------------------------------------------
-template <int TM, int KS>
+// POOLED: the operand buffers come from one LDS array shared by every instantiation inlined into the kernel
+// (k_conv_wgrad_f32_multi runs four (TM, KS) classes; static __shared__ arrays of different instantiations are NOT overlaid by
+// the compiler: 4 x ~32 KB = 128 KB would leave one block per CU instead of three)
+__device__ __forceinline__ float* wgrad_f32_lds_pool() {
+    __shared__ __attribute__((aligned(16))) float pool[2 * 16 * (144 + 144)];     // the TM = 128 size: KU * PS * (PP + PQ)
+    return pool;
+}
+
+template <int TM, int KS, bool POOLED = false>
 __device__ __forceinline__ void conv_wgrad_f32_body(const WgP& p, const int blk_id, const int blk_count) {
     constexpr int TN = 128, KU = 2, PS = 16;             // k tile, sub-steps per stage, pixels per sub-step
     constexpr int WM = (TM == 128) ? 2 : 1, WN = 4 / WM;
@@ -2029,7 +2037,14 @@ __device__ __forceinline__ void conv_wgrad_f32_body(const WgP& p, const int blk_
     constexpr int PP = ((TM + 16) % 32 == 16) ? TM + 16 : TM + 32, PQ = TN + 16;     // row pitches (floats), = 16 mod 32
     constexpr int CPR = TM / 4;                          // dy chunks (4 floats) per pixel row
     constexpr int NP = (PS * CPR + CONV_T - 1) / CONV_T; // dy chunks per thread per sub-step
-    __shared__ __attribute__((aligned(16))) float smem[KU * PS * (PP + PQ)];
+    float* smem;
+    if constexpr (POOLED) {
+        static_assert(KU * PS * (PP + PQ) <= 2 * 16 * (144 + 144), "wgrad_f32_lds_pool too small");
+        smem = wgrad_f32_lds_pool();
+    } else {
+        __shared__ __attribute__((aligned(16))) float own[KU * PS * (PP + PQ)];
+        smem = own;
+    }
     float* sP = smem;
     float* sQ = smem + KU * PS * PP;
     const float* __restrict__ xg = reinterpret_cast<const float*>(p.x);
@@ -2376,8 +2391,10 @@ static int try_launch_wgrad_patch_f32(cr_ctx* ctx, WgP& p, int ks) {
     return CR_OK;
 }
 
-template <int KS>
-static int launch_wgrad_f32_ks(cr_ctx* ctx, WgP& p) {
+// split plan of ONE f32 weight gradient launched alone (launch_wgrad_f32_ks; in deterministic mode also every member of a
+// cr_conv2d_bwd_weight_multi group, whose slabs must be those of its solo launch): sets p.steps_per_split / p.tm / p.tn,
+// returns the tile height, *splits_out = pixel splits (the grid is p.tm * p.tn * splits blocks)
+static int plan_wgrad_f32(WgP& p, int KS, int* splits_out) {
     constexpr int PS = 16;
     const int nsteps = (p.M + PS - 1) / PS;
     const int tn = (int)cr_cdiv(p.Kdim, 128);
@@ -2405,8 +2422,16 @@ static int launch_wgrad_f32_ks(cr_ctx* ctx, WgP& p) {
     p.steps_per_split = (nsteps + splits - 1) / splits;
     p.steps_per_split = (p.steps_per_split + 1) & ~1;            // whole stages (KU = 2 sub-steps)
     splits = (nsteps + p.steps_per_split - 1) / p.steps_per_split;
-    dim3 grid(tm * tn * splits);
     p.tm = tm; p.tn = tn;
+    *splits_out = splits;
+    return TM;
+}
+
+template <int KS>
+static int launch_wgrad_f32_ks(cr_ctx* ctx, WgP& p) {
+    int splits;
+    const int TM = plan_wgrad_f32(p, KS, &splits);
+    dim3 grid(p.tm * p.tn * splits);
     size_t ws_off = 0;
     const bool slabs = wgrad_use_slabs(ctx, p, splits, &ws_off);
     if (TM == 128) hipLaunchKernelGGL((k_conv_wgrad_f32<128, KS>), grid, dim3(CONV_T), 0, ctx->stream, p);
@@ -3098,6 +3123,139 @@ extern "C" int cr_conv2d_bwd_weight_group(cr_ctx* ctx, int n, const void* const*
         for (int i = 0; i < n; ++i) wgrad_reduce_slabs(ctx, g.p[i], counts[i] / tiles);
     CR_LAUNCH_CHECK();
     return CR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// cr_conv2d_bwd_weight_multi: a QUEUE of weight gradients (any mix of shapes) flushed in few launches.  Nothing reads a weight
+// gradient before the optimizer (or the all-reduce of its segment), so the caller collects the backward pass's calls and hands
+// them over together.  A problem that launch_wgrad_f32_ks would take alone (fp32, k in {1,3}, >= 64 output channels, not a
+// patch-kernel layer) joins a grid of up to CR_MAX_GROUP problems: every block runs the unchanged conv_wgrad_f32_body<TM, KS>
+// of its own problem (the class branch is block-uniform).  Alone, a 128 -> 128 3x3 layer at 64 x 64 has 18 tiles and needs 42
+// pixel splits to fill the chip: ~390 pixels per block, then the whole tile goes to dW with atomics, 42 times per element.
+// In a group of 8 a problem gets 1/8 of the resident blocks: 8 x the pixels per block, 1/8 of the atomics, one prologue and
+// tail per group.  Everything else (stem patch kernels, bf16 / split modes, 7x7, 16- and 32-channel layers) runs through the
+// single-problem route from inside this call, in queue order.
+// ---------------------------------------------------------------------------
+struct WgMulti { WgP p[CR_MAX_GROUP]; int start[CR_MAX_GROUP], count[CR_MAX_GROUP], cls[CR_MAX_GROUP]; int n; };
+
+__global__ __launch_bounds__(CONV_T) void k_conv_wgrad_f32_multi(WgMulti g) {
+    int i = 0;
+    while (i + 1 < g.n && (int)blockIdx.x >= g.start[i + 1]) ++i;
+    const int blk = (int)blockIdx.x - g.start[i];
+    if (blk >= g.count[i]) return;
+    switch (g.cls[i]) {                    // (TM == 128) * 2 + (KS == 3)
+    case 0: conv_wgrad_f32_body<64, 1, true>(g.p[i], blk, g.count[i]); break;
+    case 1: conv_wgrad_f32_body<64, 3, true>(g.p[i], blk, g.count[i]); break;
+    case 2: conv_wgrad_f32_body<128, 1, true>(g.p[i], blk, g.count[i]); break;
+    default: conv_wgrad_f32_body<128, 3, true>(g.p[i], blk, g.count[i]); break;
+    }
+}
+
+// One plan for a whole group in atomic mode: about one resident round (3 x 256 blocks) over all problems, pixel ranges sized
+// so that every block issues about the same number of MFMAs (a 128-row tile costs twice a 64-row one per sub-step), >= 8
+// sub-steps per block.  Tile height: 128 rows from 128 output channels on.  The 64-row exceptions of plan_wgrad_f32 bought
+// their gain by halving the pixel splits (= the atomics) of a solo launch; a group member already has several times fewer.
+// Measured inside a group: eight 128 -> 128 3x3 layers at 4 x 64 x 64 take 352 us on 128-row tiles, 416 us on 64-row tiles
+// (463 us as eight solo launches); six layers of 128 / 256 channels with two Root 1x1 layers 313 us against 578 us.
+static void plan_wgrad_f32_group(WgP* ps, int n, int* TMs, int* splits) {
+    constexpr int PS = 16;
+    int nsteps[CR_MAX_GROUP], tiles[CR_MAX_GROUP];
+    int64_t work = 0;                      // in (64-row tile, sub-step) units
+    for (int i = 0; i < n; ++i) {
+        WgP& p = ps[i];
+        TMs[i] = p.Cout >= 128 ? 128 : 64;
+        p.tm = (int)cr_cdiv(p.Cout, TMs[i]); p.tn = (int)cr_cdiv(p.Kdim, 128);
+        tiles[i] = p.tm * p.tn;
+        nsteps[i] = (p.M + PS - 1) / PS;
+        work += (int64_t)tiles[i] * nsteps[i] * (TMs[i] / 64);
+    }
+    int64_t per_block = cr_cdiv(work, 768);
+    for (int it = 0; it < 6; ++it) {       // rounding up each problem's splits can overshoot the round: a block count just
+        int64_t total = 0;                 // above 768 costs a second round (see plan_wgrad_f32), so grow the ranges a little
+        for (int i = 0; i < n; ++i) {
+            int sps = (int)cr_cdiv(per_block, TMs[i] / 64);
+            if (sps < 8) sps = 8;
+            sps = (sps + 1) & ~1;          // whole stages (KU = 2 sub-steps)
+            ps[i].steps_per_split = sps;
+            splits[i] = (int)cr_cdiv(nsteps[i], sps);
+            total += ((int64_t)tiles[i] * splits[i] + 7) & ~(int64_t)7;      // as group_starts pads the grid
+        }
+        if (total <= 768) break;
+        per_block = cr_cdiv(per_block * total, 768) + 1;
+    }
+    // Measured and not kept: filling the round up afterwards with one more split for the members with the longest blocks
+    // (eight 128 -> 128 3x3 layers at 4 x 64 x 64: 765 blocks of 94 / 104 sub-steps instead of 720 of 104) -- 352 -> 458 us;
+    // blocks of unequal length and a padded grid above 768 cost more than the idle slots.
+}
+
+static int launch_wgrad_f32_multi(cr_ctx* ctx, WgMulti& g, const int* splits) {
+    int counts[CR_MAX_GROUP];
+    for (int i = 0; i < g.n; ++i) counts[i] = g.p[i].tm * g.p[i].tn * splits[i];
+    const int total = group_starts(g.n, counts, g.start);
+    for (int i = 0; i < g.n; ++i) g.count[i] = counts[i];
+    for (int i = g.n; i < CR_MAX_GROUP; ++i) { g.start[i] = total; g.count[i] = 0; g.cls[i] = 0; }
+    hipLaunchKernelGGL(k_conv_wgrad_f32_multi, dim3((unsigned)total), dim3(CONV_T), 0, ctx->stream, g);
+    for (int i = 0; i < g.n; ++i)
+        if (g.p[i].slab) wgrad_reduce_slabs(ctx, g.p[i], splits[i]);
+    CR_LAUNCH_CHECK();
+    g.n = 0;
+    return CR_OK;
+}
+
+extern "C" int cr_conv2d_bwd_weight_multi(cr_ctx* ctx, int n, const void* const* dys, const void* const* xs, float* const* dws,
+                                          float* const* dbiases, const int* Ns, const int* Hs, const int* Ws, const int* Cins,
+                                          const int* Couts, const int* kss, const int* strides, const int* pads, int act_f32) {
+    CR_CHECK_ARG(ctx && dys && xs && dws && Ns && Hs && Ws && Cins && Couts && kss && strides && pads,
+                 "cr_conv2d_bwd_weight_multi: NULL pointer");
+    CR_CHECK_ARG(n >= 1, "cr_conv2d_bwd_weight_multi: n >= 1");
+    const bool det = deterministic_on() && ctx->ws;
+    WgMulti g;
+    g.n = 0;
+    int splits[CR_MAX_GROUP], TMs[CR_MAX_GROUP];
+    size_t ws_off = 0;
+    int rc;
+    // atomic mode: the group is planned as a whole when it is launched; deterministic mode: every member keeps the plan and
+    // the slabs of its solo launch (the body's summation order depends on the split boundaries only -> bit-equal results)
+    auto flush = [&]() -> int {
+        ws_off = 0;
+        if (g.n == 0) return CR_OK;
+        if (!det) plan_wgrad_f32_group(g.p, g.n, TMs, splits);
+        for (int i = 0; i < g.n; ++i) g.cls[i] = (TMs[i] == 128 ? 2 : 0) + (g.p[i].Kdim == 9 * g.p[i].Cin ? 1 : 0);
+        return launch_wgrad_f32_multi(ctx, g, splits);
+    };
+    for (int i = 0; i < n; ++i) {
+        float* const dbias = dbiases ? dbiases[i] : nullptr;
+        const int N = Ns[i], H = Hs[i], W = Ws[i], Cin = Cins[i], Cout = Couts[i], ks = kss[i], stride = strides[i], pad = pads[i];
+        bool grouped = act_f32 == 1 && dys[i] && xs[i] && dws[i] && (ks == 1 || ks == 3) && Cout >= 64;
+        WgP p{};
+        if (grouped) {
+            if ((rc = conv_common_checks("cr_conv2d_bwd_weight_multi", N, H, W, Cin, Cout, ks, stride, pad, act_f32))) return rc;
+            const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
+            p = make_wgrad_params(dys[i], xs[i], dws[i], N, H, W, Cin, Ho, Wo, Cout, ks, stride, pad, act_f32);
+            p.dbias = dbias;
+            if (det) {
+                int sp;
+                const int TM = plan_wgrad_f32(p, ks, &sp);
+                grouped = TM >= 64;
+                if (grouped && !wgrad_use_slabs(ctx, p, sp, &ws_off)) {
+                    // the workspace is full: cut the group here and give this problem the start of the workspace; one whose
+                    // slabs do not fit at all runs alone on atomics, as it always did (never slabs and atomics in one grid)
+                    if ((rc = flush())) return rc;
+                    grouped = wgrad_use_slabs(ctx, p, sp, &ws_off);
+                }
+                if (grouped) { TMs[g.n] = TM; splits[g.n] = sp; }
+            }
+        }
+        if (!grouped) {                    // the single-problem route, in queue order
+            if ((rc = flush())) return rc;
+            if ((rc = conv2d_bwd_weight_impl(ctx, dys[i], xs[i], dws[i], dbias, N, H, W, Cin, Cout, ks, stride, pad, 1, act_f32)))
+                return rc;
+            continue;
+        }
+        g.p[g.n++] = p;
+        if (g.n == CR_MAX_GROUP && (rc = flush())) return rc;
+    }
+    return flush();
 }
 
 // ---------------------------------------------------------------------------

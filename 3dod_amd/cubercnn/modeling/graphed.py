@@ -185,7 +185,17 @@ class GraphedDense(GraphOwner):
             return [p for m in mods for p in m.parameters() if p.requires_grad and ((id(p) not in low) == first)]
         self.segment_params = segment_params
 
+        # both backward segments queue their fp32 weight gradients and launch them in groups (ops.deferred_wgrad); each
+        # segment flushes before its graph ends, so mid_bwd's all-reduce sees final gradients
         def run_backward(outs, grads):
+            with ops.deferred_wgrad():
+                return _run_backward(outs, grads)
+
+        def run_backward2(gx):
+            with ops.deferred_wgrad():
+                _run_backward2(gx)
+
+        def _run_backward(outs, grads):
             # torch.autograd.grad, not .backward(): no AccumulateGrad nodes (they are pinned to the stream they were
             # first created on, which breaks capture).  Conv / BN kernels accumulate into the flat gradient
             # themselves and return None; what comes back here went through plain autograd (biases, the stem and
@@ -218,7 +228,7 @@ class GraphedDense(GraphOwner):
             assert res[-1] is not None, "two-segment backward: no gradient reaches the trunk"
             return res[-1]
 
-        def run_backward2(gx):
+        def _run_backward2(gx):
             low = lower_ids()
             ps2 = [p for p in leaves() if id(p) in low]
             res = torch.autograd.grad([cut["x"]], ps2, [gx], allow_unused=True)

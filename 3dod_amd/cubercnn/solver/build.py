@@ -16,6 +16,7 @@ import torch
 import torch.distributed as dist
 
 from ... import hipops as ops
+from ...hipops import deferred_wgrad        # not through `ops`: a CPU backend installed there has no kernels to defer
 from ..modeling.graphed import GraphOwner as _GraphOwner
 
 NORM_TYPES = (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d, torch.nn.BatchNorm3d, torch.nn.SyncBatchNorm,
@@ -404,7 +405,8 @@ class TrainStep:
             self.__dict__.pop("_rest_cache", None)
             g.mid_bwd = self._mid_allreduce
         self._early_done = self._mid_done = False
-        losses.backward()
+        with deferred_wgrad():              # the eager convolutions' weight gradients, launched in groups
+            losses.backward()
         opt.collect_grads()
         # ---- gradient all-reduce (DDP, train_net.py:477-480), bucketed, on a side stream; the RoI heads' part was
         # started before the trunk's backward graph (see _early_allreduce) when the dense-region graphs are active

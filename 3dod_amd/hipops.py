@@ -15,6 +15,7 @@ bfloat16 and the contractions run on the bf16 MFMA with f32 accumulation.  Every
 takes its mode from the dtype of the tensor it is handed, so both modes can coexist
 in one process (the parity tests run them side by side).
 """
+import contextlib
 import ctypes
 import os
 
@@ -325,12 +326,64 @@ def grad_sink(t):
     return getattr(t, "_cr_grad", None)
 
 
+# Deferred weight gradients.  Nothing reads a weight gradient before the optimizer (with several GPUs: before the all-reduce of
+# its backward segment), so inside deferred_wgrad() the fp32 calls that accumulate into a gradient sink are queued instead of
+# launched, and flushed WGRAD_GROUP at a time through cr_conv2d_bwd_weight_multi: several layers share one grid, every block
+# covers a longer pixel range and pays its atomics once (csrc/conv.hip).  The queue keeps dy / x alive until they are launched.
+WGRAD_GROUP = 8
+_WGRAD_DEPTH = [0]
+_WGRAD_PENDING = []
+
+
+def wgrad_pending():
+    """number of queued weight gradients (0 outside deferred_wgrad())"""
+    return len(_WGRAD_PENDING)
+
+
+def conv_bwd_weight_multi_raw(items):
+    """items: (dy, x, dw, dbias or None, k, stride, pad), fp32 mode; dw / dbias are accumulated into, in queue order"""
+    cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
+    xs = [it[1] for it in items]
+    _lib.call("cr_conv2d_bwd_weight_multi", len(items), cast(_ptr_table([it[0] for it in items])), cast(_ptr_table(xs)),
+              cast(_ptr_table([it[2] for it in items])), cast(_ptr_table([it[3] for it in items])),
+              cast(_int_table([x.shape[0] for x in xs])), cast(_int_table([x.shape[1] for x in xs])),
+              cast(_int_table([x.shape[2] for x in xs])), cast(_int_table([x.shape[3] for x in xs])),
+              cast(_int_table([it[0].shape[3] for it in items])), cast(_int_table([it[4] for it in items])),
+              cast(_int_table([it[5] for it in items])), cast(_int_table([it[6] for it in items])), 1, device=xs[0].device)
+
+
+def wgrad_flush():
+    """launch what is queued.  The queue is emptied first: a failing launch raises, it never leaves entries behind."""
+    if _WGRAD_PENDING:
+        items = list(_WGRAD_PENDING)
+        del _WGRAD_PENDING[:]
+        conv_bwd_weight_multi_raw(items)
+
+
+@contextlib.contextmanager
+def deferred_wgrad():
+    """queue the fp32 sink-accumulating weight gradients of the enclosed backward pass (conv_bwd_weight_raw) and launch them
+    in groups.  Everything queued is launched before the context is left -- also when an exception passes through: a gradient
+    is never dropped.  Re-entrant; an inner exit flushes too."""
+    _WGRAD_DEPTH[0] += 1
+    try:
+        yield
+    finally:
+        _WGRAD_DEPTH[0] -= 1
+        wgrad_flush()
+
+
 def conv_bwd_weight_raw(dy, x, k, stride, pad, sink=None, bias_acc=None):
     """dW (into `sink` when given).  bias_acc: f32 [Cout] buffer that additionally receives += sum_pixels dy (fused)."""
     N, H, W, Cin = x.shape
     Cout = dy.shape[3]
     af = _af(x)
     assert dy.dtype == x.dtype
+    if sink is not None and af == 1 and _WGRAD_DEPTH[0] > 0:
+        _WGRAD_PENDING.append((dy, x, sink, bias_acc, k, stride, pad))
+        if len(_WGRAD_PENDING) >= WGRAD_GROUP:
+            wgrad_flush()
+        return None
     if bias_acc is not None:
         dw = sink if sink is not None else torch.empty((Cout, Cin, k, k), dtype=f32, device=x.device).contiguous(
             memory_format=torch.channels_last)

@@ -343,6 +343,14 @@ int cr_conv2d_bwd_data_group(cr_ctx* ctx, int n, const void* const* dys, const v
 int cr_conv2d_bwd_weight_group(cr_ctx* ctx, int n, const void* const* dys, const void* const* xs, float* const* dws,
                                float* const* dbiases, const int* Ns, const int* Hs, const int* Ws, int Cin, int Cout, int ks,
                                int pad, int act_f32);
+/* A queue of n >= 1 weight gradients of ANY mix of shapes, run in queue order: dws[i] += dys[i]^T xs[i] (and, where given,
+ * dbiases[i] += column sums of dys[i]); ALWAYS accumulates; dws / dbiases entries may repeat.  All arguments but act_f32 are
+ * HOST arrays of n entries (dbiases may be NULL).  fp32 problems with k in {1,3} and >= 64 output channels share grids of up
+ * to 8 problems (csrc/conv.hip: k_conv_wgrad_f32_multi); every other problem takes the route of cr_conv2d_bwd_weight[_bias]
+ * from inside the call.  CR_DETERMINISTIC=1: bit-equal to the same problems run one by one through cr_conv2d_bwd_weight. */
+int cr_conv2d_bwd_weight_multi(cr_ctx* ctx, int n, const void* const* dys, const void* const* xs, float* const* dws,
+                               float* const* dbiases, const int* Ns, const int* Hs, const int* Ws, const int* Cins,
+                               const int* Couts, const int* kss, const int* strides, const int* pads, int act_f32);
 int cr_cast_f32_to_bf16(cr_ctx* ctx, const float* src, void* dst, int64_t n);
 /* bias gradient: out[c] += sum_m x[m][c]; x (M,C) bf16 or f32; ws = 1024*C floats; deterministic. */
 int cr_colsum_accum(cr_ctx* ctx, const void* x, int is_f32, int64_t M, int C, float* ws, float* out);

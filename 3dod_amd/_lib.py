@@ -59,6 +59,7 @@ SIGNATURES = {
     "cr_colsum_accum": [P, P, c_int, c_int64, c_int, P, P],
     "cr_bn_fwd": [P, P, P, c_int, P, P, P, P, c_int64, c_int, c_int, c_float, c_float, P, P, P, c_int],
     "cr_bn_bwd": [P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int, c_int, c_int],
+    "cr_bn_bwd_mask": [P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int, c_int, c_int],
     "cr_bn_frozen_unfold": [P, P, P, P, P, P, P, c_float, P, c_int, P, P, c_int, c_int],
     "cr_pool2x_fwd": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int],
     "cr_pool2x_bwd": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P],

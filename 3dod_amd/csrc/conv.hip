@@ -3506,16 +3506,12 @@ extern "C" int cr_fc_grad_accum(cr_ctx* ctx, const void* g, float* acc, int O, i
 // finalize: per-tile partials [nparts][2][C] -> mean / invstd (+ running stats update, momentum, unbiased var).
 // One workgroup per channel; strided serial sums + a fixed-order LDS tree, in double: reproducible and accurate
 // (no E[x^2]-E[x]^2 cancellation at float precision).
-__global__ __launch_bounds__(256) void k_bn_finalize(const float* __restrict__ stats, int nparts, int C, float count,
-                                                     float eps, float momentum, float* __restrict__ mean_invstd,
-                                                     float* __restrict__ running_mean, float* __restrict__ running_var) {
+// bn_finalize_tail: the 256 lane sums (s, q) of channel c -> the 128 -> 1 tree and the final arithmetic (the whole block calls it)
+__device__ __forceinline__ void bn_finalize_tail(double s, double q, int c, int C, float count, float eps, float momentum,
+                                                 float* __restrict__ mean_invstd, float* __restrict__ running_mean,
+                                                 float* __restrict__ running_var) {
     __shared__ double ss[256], sq[256];
-    const int c = blockIdx.x, t = threadIdx.x;
-    double s = 0.0, q = 0.0;
-    for (int r = t; r < nparts; r += 256) {
-        s += (double)stats[(size_t)r * 2 * C + c];
-        q += (double)stats[(size_t)r * 2 * C + C + c];
-    }
+    const int t = threadIdx.x;
     ss[t] = s; sq[t] = q;
     __syncthreads();
     for (int off = 128; off > 0; off >>= 1) {
@@ -3523,18 +3519,80 @@ __global__ __launch_bounds__(256) void k_bn_finalize(const float* __restrict__ s
         __syncthreads();
     }
     if (t == 0) {
+        // the fused multiply-adds are the ones the compiler formed from the plain expressions, now written out (the order is
+        // part of what tests/test_gpu_bn_finalize_order.py specifies)
+#pragma clang fp contract(off)
         const double mean = ss[0] / (double)count;
-        double var = sq[0] / (double)count - mean * mean;
+        double var = __builtin_fma(-mean, mean, sq[0] / (double)count);
         if (var < 0.0) var = 0.0;
         mean_invstd[c] = (float)mean;
         mean_invstd[C + c] = (float)(1.0 / sqrt(var + (double)eps));
         if (running_mean) {
             const double unbiased = count > 1.f ? var * (double)count / ((double)count - 1.0) : var;
-            running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
-            running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unbiased);
+            running_mean[c] = (float)__builtin_fma((double)momentum, mean, (1.0 - momentum) * running_mean[c]);
+            running_var[c] = (float)__builtin_fma((double)momentum, unbiased, (1.0 - momentum) * running_var[c]);
         }
     }
 }
+
+__global__ __launch_bounds__(256) void k_bn_finalize(const float* __restrict__ stats, int nparts, int C, float count,
+                                                     float eps, float momentum, float* __restrict__ mean_invstd,
+                                                     float* __restrict__ running_mean, float* __restrict__ running_var) {
+    const int c = blockIdx.x, t = threadIdx.x;
+    double s = 0.0, q = 0.0;
+    for (int r = t; r < nparts; r += 256) {
+        s += (double)stats[(size_t)r * 2 * C + c];
+        q += (double)stats[(size_t)r * 2 * C + C + c];
+    }
+    bn_finalize_tail(s, q, c, C, count, eps, momentum, mean_invstd, running_mean, running_var);
+}
+
+// The same finalize in two launches for the layers with many statistics rows (the 512 x 512 and 256 x 256 maps): above, the C
+// workgroups each walk ALL rows to pick 2 floats out of every 8C-byte row, so every 128 bytes of them are fetched 16 times.  Here
+// step 1 reads every row once: thread (row lane t of 256, column j of 2C) adds rows t, t + 256, ... ascending in double --
+// the sum thread t of k_bn_finalize forms for that column, bit for bit -- into lanes[t][j]; consecutive threads take
+// consecutive columns, so a wave reads whole rows.  Step 2 runs the tree and the arithmetic of the tail over those 256 doubles.
+static constexpr int BN_LANE_BATCH = 8;     // loads in flight per thread in step 1 (the additions stay in row order)
+__global__ __launch_bounds__(256) void k_bn_stats_lanes(const float* __restrict__ stats, int nparts, int C2,
+                                                        double* __restrict__ lanes) {
+    const int f = blockIdx.x * 256 + threadIdx.x;         // < 256 * C2 (grid = C2 blocks)
+    const int t = f / C2, j = f - t * C2;
+    const float* p = stats + (size_t)t * C2 + j;
+    const size_t step = (size_t)256 * C2;
+    double s = 0.0;
+    int r = t;
+    for (; r + 256 * (BN_LANE_BATCH - 1) < nparts; r += 256 * BN_LANE_BATCH) {
+        float v[BN_LANE_BATCH];
+#pragma unroll
+        for (int u = 0; u < BN_LANE_BATCH; ++u) v[u] = p[(size_t)u * step];
+#pragma unroll
+        for (int u = 0; u < BN_LANE_BATCH; ++u) s += (double)v[u];
+        p += BN_LANE_BATCH * step;
+    }
+    for (; r < nparts; r += 256) { s += (double)*p; p += step; }
+    lanes[f] = s;
+}
+
+__global__ __launch_bounds__(256) void k_bn_finalize_lanes(const double* __restrict__ lanes, int C, float count, float eps,
+                                                           float momentum, float* __restrict__ mean_invstd,
+                                                           float* __restrict__ running_mean, float* __restrict__ running_var) {
+    const int c = blockIdx.x, t = threadIdx.x;
+    bn_finalize_tail(lanes[(size_t)t * 2 * C + c], lanes[(size_t)t * 2 * C + C + c], c, C, count, eps, momentum, mean_invstd,
+                     running_mean, running_var);
+}
+
+// The forward's value before the residual and the ReLU, in the one form every kernel below uses: subtract, multiply, then ONE
+// fused multiply-add (what the compiler made of the plain expression, now pinned).  The backward of a ReLU layer without a
+// residual recomputes it from x to get the ReLU mask instead of reading the forward's output, so the bits must agree.
+__device__ __forceinline__ float bn_affine(float x, float mean, float invstd, float gamma, float beta) {
+#pragma clang fp contract(off)
+    const float xh = (x - mean) * invstd;
+    return __builtin_fmaf(xh, gamma, beta);
+}
+// whether the forward STORED a positive value for the pre-activation v (no residual): the ReLU, then the rounding of the store
+template <typename T> __device__ __forceinline__ bool bn_relu_on(float v);
+template <> __device__ __forceinline__ bool bn_relu_on<float>(float v) { return fmaxf(v, 0.f) > 0.f; }
+template <> __device__ __forceinline__ bool bn_relu_on<u16>(float v) { return bf2f(f2bf(fmaxf(v, 0.f))) > 0.f; }
 
 // y = relu?( (x - mean) * invstd * gamma + beta (+ residual) ), 8 channels per thread
 template <typename T>
@@ -3552,7 +3610,7 @@ __global__ __launch_bounds__(256) void k_bn_apply(const T* __restrict__ x, const
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int c = c0 + e;
-            float t = (xv[e] - mean_invstd[c]) * mean_invstd[C + c] * gamma[c] + beta[c];
+            float t = bn_affine(xv[e], mean_invstd[c], mean_invstd[C + c], gamma[c], beta[c]);
             if (res) t += rv[e];
             o[e] = relu ? fmaxf(t, 0.f) : t;
         }
@@ -3620,7 +3678,7 @@ __global__ __launch_bounds__(256) void k_bn_apply_fused(const T* __restrict__ x,
         if (res) load8<T>(res, i8, rv);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            float v = (xv[e] - mu[e]) * is8[e] * ga[e] + be[e];        // as k_bn_apply
+            float v = bn_affine(xv[e], mu[e], is8[e], ga[e], be[e]);   // as k_bn_apply
             if (res) v += rv[e];
             o[e] = relu ? fmaxf(v, 0.f) : v;
         }
@@ -3630,6 +3688,8 @@ __global__ __launch_bounds__(256) void k_bn_apply_fused(const T* __restrict__ x,
 
 // at most this many statistics rows take the fused finalize + apply (k_bn_apply_fused): the 64x64 and smaller maps
 static constexpr int BN_FUSE_ROWS = 256;
+// from this many statistics rows on the unfused finalize runs as k_bn_stats_lanes + k_bn_finalize_lanes
+static constexpr int BN_LANES_MIN_ROWS = 2048;
 
 extern "C" int cr_bn_fwd(cr_ctx* ctx, const void* x, const float* stats, int nparts, const float* gamma,
                          const float* beta, const void* residual, void* y, int64_t M, int C, int relu, float eps,
@@ -3654,8 +3714,17 @@ extern "C" int cr_bn_fwd(cr_ctx* ctx, const void* x, const float* stats, int npa
         CR_LAUNCH_CHECK();
         return CR_OK;
     }
-    hipLaunchKernelGGL(k_bn_finalize, dim3((unsigned)C), dim3(256), 0, ctx->stream, stats, nparts, C, (float)M, eps,
-                       momentum, mean_invstd, running_mean, running_var);
+    const size_t lanes_bytes = sizeof(double) * 256 * 2 * C;
+    if (nparts >= BN_LANES_MIN_ROWS && ctx->ws && lanes_bytes <= ctx->ws_bytes) {
+        double* lanes = (double*)ctx->ws;                // written and read by this call's two launches only
+        hipLaunchKernelGGL(k_bn_stats_lanes, dim3((unsigned)(2 * C)), dim3(256), 0, ctx->stream, stats, nparts, 2 * C, lanes);
+        CR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_bn_finalize_lanes, dim3((unsigned)C), dim3(256), 0, ctx->stream, lanes, C, (float)M, eps,
+                           momentum, mean_invstd, running_mean, running_var);
+    } else {
+        hipLaunchKernelGGL(k_bn_finalize, dim3((unsigned)C), dim3(256), 0, ctx->stream, stats, nparts, C, (float)M, eps,
+                           momentum, mean_invstd, running_mean, running_var);
+    }
     CR_LAUNCH_CHECK();
     const int64_t total = M * (C >> 3);
     const unsigned grid = (unsigned)(cr_cdiv(total, 256) < 4096 ? cr_cdiv(total, 256) : 4096);
@@ -3670,35 +3739,52 @@ extern "C" int cr_bn_fwd(cr_ctx* ctx, const void* x, const float* stats, int npa
 }
 
 // backward reduce: g = dy * (relu ? out > 0 : 1);  partial[block][0][c] = sum g ; partial[block][1][c] = sum g*xhat
+// All three backward kernels: MASKX (always a ReLU layer, without a residual, out == NULL) takes the mask from bn_affine(x)
+// instead -- the value the forward stored, bit for bit -- and saves the pass over out; beta is only read in that case.
+// The mask needs gamma and beta of every channel a thread owns on top of mean / invstd, so a MASKX thread owns BNB_V = 4
+// channels, not 8: half the per-channel constants and half the loaded values per thread, which keeps these kernels below the
+// register count of the ones that read out.  The reduce kernel then runs 512 threads, so that a block still covers the same
+// rows and every channel's sum is formed over the same rows in the same order: the same bits.
 #define BNB_MAXBLOCKS 1024
-template <typename T>
-__global__ __launch_bounds__(256) void k_bn_bwd_reduce(const T* __restrict__ dy, const T* __restrict__ out,
+#define BNB_V (MASKX ? 4 : 8)
+#define BNB_VSHIFT (MASKX ? 2 : 3)
+template <typename T, bool MASKX>
+__global__ __launch_bounds__(MASKX ? 512 : 256) void k_bn_bwd_reduce(const T* __restrict__ dy, const T* __restrict__ out,
                                                        const T* __restrict__ x, const float* __restrict__ mean_invstd,
+                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
                                                        float* __restrict__ partial, int64_t M, int C, int relu) {
     extern __shared__ float s_acc[];        // [rows_per_block][2][C]  (= 4096 floats for every supported C)
-    const int cg = C >> 3;
+    constexpr int V = BNB_V;                // channels per thread; blockDim.x = 256 * 8 / V
+    const int cg = C >> BNB_VSHIFT;
     const int mycg = threadIdx.x % cg, myrow = threadIdx.x / cg;
     const int rows_per_block = blockDim.x / cg;
-    const int c0 = mycg << 3;
-    float a[8], b[8], mu[8], is[8];
+    const int c0 = mycg << BNB_VSHIFT;
+    float a[V], b[V], mu[V], is[V];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { a[e] = 0.f; b[e] = 0.f; mu[e] = mean_invstd[c0 + e]; is[e] = mean_invstd[C + c0 + e]; }
+    for (int e = 0; e < V; ++e) { a[e] = 0.f; b[e] = 0.f; mu[e] = mean_invstd[c0 + e]; is[e] = mean_invstd[C + c0 + e]; }
+    float ga[V], be[V];
+    if (MASKX) {
+#pragma unroll
+        for (int e = 0; e < V; ++e) { ga[e] = gamma[c0 + e]; be[e] = beta[c0 + e]; }
+    }
     for (int64_t m = (int64_t)blockIdx.x * rows_per_block + myrow; m < M; m += (int64_t)gridDim.x * rows_per_block) {
-        const size_t i8 = (size_t)(m * cg + mycg) * 8;
-        float dv[8], xv[8], ov[8];
-        load8<T>(dy, i8, dv);
-        load8<T>(x, i8, xv);
-        if (relu) load8<T>(out, i8, ov);
+        const size_t i8 = (size_t)(m * cg + mycg) * V;
+        float dv[V], xv[V], ov[V];
+        loadv<T, V>(dy, i8, dv);
+        loadv<T, V>(x, i8, xv);
+        if (relu && !MASKX) loadv<T, V>(out, i8, ov);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float gq = (!relu || ov[e] > 0.f) ? dv[e] : 0.f;
+        for (int e = 0; e < V; ++e) {
+            const bool on = MASKX ? bn_relu_on<T>(bn_affine(xv[e], mu[e], is[e], ga[e], be[e]))
+                                  : (!relu || ov[e] > 0.f);
+            const float gq = on ? dv[e] : 0.f;
             const float xh = (xv[e] - mu[e]) * is[e];
             a[e] += gq;
             b[e] += gq * xh;
         }
     }
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { s_acc[(myrow * 2 + 0) * C + c0 + e] = a[e]; s_acc[(myrow * 2 + 1) * C + c0 + e] = b[e]; }
+    for (int e = 0; e < V; ++e) { s_acc[(myrow * 2 + 0) * C + c0 + e] = a[e]; s_acc[(myrow * 2 + 1) * C + c0 + e] = b[e]; }
     __syncthreads();
     float* dst = partial + (size_t)blockIdx.x * 2 * C;
     for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
@@ -3735,43 +3821,46 @@ __global__ __launch_bounds__(256) void k_bn_bwd_finalize(const float* __restrict
 }
 
 // dx = gamma*invstd*(g - sum_g/M - xhat*sum_gx/M); also writes g (the masked grad) for the residual branch
-template <typename T>
+template <typename T, bool MASKX>
 __global__ __launch_bounds__(256) void k_bn_bwd_apply(const T* __restrict__ dy, const T* __restrict__ out,
                                                       const T* __restrict__ x, const float* __restrict__ mean_invstd,
-                                                      const float* __restrict__ gamma, const float* __restrict__ sums,
-                                                      T* __restrict__ dx, T* __restrict__ dres, int64_t M, int C,
-                                                      int relu) {
-    const int cg = C >> 3;
+                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                      const float* __restrict__ sums, T* __restrict__ dx,
+                                                      T* __restrict__ dres, int64_t M, int C, int relu) {
+    constexpr int V = BNB_V;
+    const int cg = C >> BNB_VSHIFT;
     const float invM = 1.f / (float)M;
     const int64_t total = M * cg;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int c0 = (int)(i % cg) << 3;
-        const size_t i8 = (size_t)i * 8;
-        float dv[8], xv[8], ov[8], vd[8], vg[8];
-        load8<T>(dy, i8, dv);
-        load8<T>(x, i8, xv);
-        if (relu) load8<T>(out, i8, ov);
+        const int c0 = (int)(i % cg) << BNB_VSHIFT;
+        const size_t i8 = (size_t)i * V;
+        float dv[V], xv[V], ov[V], vd[V], vg[V];
+        loadv<T, V>(dy, i8, dv);
+        loadv<T, V>(x, i8, xv);
+        if (relu && !MASKX) loadv<T, V>(out, i8, ov);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
+        for (int e = 0; e < V; ++e) {
             const int c = c0 + e;
-            const float gq = (!relu || ov[e] > 0.f) ? dv[e] : 0.f;
             const float is = mean_invstd[C + c];
+            const bool on = MASKX ? bn_relu_on<T>(bn_affine(xv[e], mean_invstd[c], is, gamma[c], beta[c])) : (!relu || ov[e] > 0.f);
+            const float gq = on ? dv[e] : 0.f;
             const float xh = (xv[e] - mean_invstd[c]) * is;
             vd[e] = gamma[c] * is * (gq - sums[c] * invM - xh * sums[C + c] * invM);
             vg[e] = gq;
         }
-        store8<T>(dx, i8, vd);
-        if (dres) store8<T>(dres, i8, vg);
+        storev<T, V>(dx, i8, vd);
+        if (dres) storev<T, V>(dres, i8, vg);
     }
 }
 
 // finalize + apply of the backward in one launch (same scheme as k_bn_apply_fused): the blocks of px chunk 0 accumulate
 // dgamma / dbeta
-template <typename T>
+template <typename T, bool MASKX>
 __global__ __launch_bounds__(256) void k_bn_bwd_apply_fused(const T* __restrict__ dy, const T* __restrict__ out,
                                                             const T* __restrict__ x, const float* __restrict__ mean_invstd,
-                                                            const float* __restrict__ gamma, const float* __restrict__ partial,
-                                                            int nparts, T* __restrict__ dx, T* __restrict__ dres,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            const float* __restrict__ partial, int nparts,
+                                                            T* __restrict__ dx, T* __restrict__ dres,
                                                             float* __restrict__ dgamma, float* __restrict__ dbeta, int64_t M,
                                                             int C, int relu, int px_per_block) {
     __shared__ double sd[2][8][32];
@@ -3800,52 +3889,51 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply_fused(const T* __restrict_
         if (blockIdx.x == 0) { dbeta[cbase + t] += sg; dgamma[cbase + t] += sgx; }
     }
     __syncthreads();
-    const int cgl = t & 3;
-    float mu[8], is8[8], ga[8], k1[8], k2[8];
+    constexpr int V = BNB_V, G = 32 / V;                 // G threads share a pixel of the slice, 256 / G pixels per pass
+    const int cgl = t & (G - 1);
+    float mu[V], is8[V], ga[V], be[V], k1[V], k2[V];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int cc = cgl * 8 + e;
+    for (int e = 0; e < V; ++e) {
+        const int cc = cgl * V + e;
         mu[e] = sc[0][cc]; is8[e] = sc[1][cc]; ga[e] = gamma[cbase + cc]; k1[e] = sc[2][cc]; k2[e] = sc[3][cc];
+        be[e] = MASKX ? beta[cbase + cc] : 0.f;
     }
     const int64_t m0 = (int64_t)blockIdx.x * px_per_block, m1 = m0 + px_per_block < M ? m0 + px_per_block : M;
-    for (int64_t m = m0 + (t >> 2); m < m1; m += 64) {
-        const size_t i8 = (size_t)m * C + cbase + cgl * 8;
-        float dv[8], xv[8], ov[8], vd[8], vg[8];
-        load8<T>(dy, i8, dv);
-        load8<T>(x, i8, xv);
-        if (relu) load8<T>(out, i8, ov);
+    for (int64_t m = m0 + t / G; m < m1; m += 256 / G) {
+        const size_t i8 = (size_t)m * C + cbase + cgl * V;
+        float dv[V], xv[V], ov[V], vd[V], vg[V];
+        loadv<T, V>(dy, i8, dv);
+        loadv<T, V>(x, i8, xv);
+        if (relu && !MASKX) loadv<T, V>(out, i8, ov);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float gq = (!relu || ov[e] > 0.f) ? dv[e] : 0.f;
+        for (int e = 0; e < V; ++e) {
+            const bool on = MASKX ? bn_relu_on<T>(bn_affine(xv[e], mu[e], is8[e], ga[e], be[e]))
+                                  : (!relu || ov[e] > 0.f);
+            const float gq = on ? dv[e] : 0.f;
             const float xh = (xv[e] - mu[e]) * is8[e];
             vd[e] = ga[e] * is8[e] * (gq - k1[e] - xh * k2[e]);
             vg[e] = gq;
         }
-        store8<T>(dx, i8, vd);
-        if (dres) store8<T>(dres, i8, vg);
+        storev<T, V>(dx, i8, vd);
+        if (dres) storev<T, V>(dres, i8, vg);
     }
 }
 
 // sums: f32 workspace of (CR_BN_BWD_WS_ROWS) x 2 x C floats (partials + the reduced [2][C] in the last row).
 // dgamma/dbeta are ACCUMULATED (+=).  No atomics: bitwise reproducible.
-extern "C" int cr_bn_bwd(cr_ctx* ctx, const void* dy, const void* out, const void* x, const float* mean_invstd,
-                         const float* gamma, float* sums, void* dx, void* dres, float* dgamma, float* dbeta,
-                         int64_t M, int C, int relu, int act_f32) {
-    CR_CHECK_ARG(ctx && dy && x && mean_invstd && gamma && sums && dx && dgamma && dbeta, "cr_bn_bwd: NULL pointer");
-    CR_CHECK_ARG(!relu || out, "cr_bn_bwd: relu needs the forward output");
-    CR_CHECK_ARG(M > 0 && C % 8 == 0 && C <= 2048 && 256 % (C >> 3) == 0, "cr_bn_bwd: unsupported C=%d", C);
+// MASKX: the ReLU mask from x (out == NULL; only then beta is read).
+template <typename T, bool MASKX>
+static int bn_bwd_launch(cr_ctx* ctx, const T* dy, const T* out, const T* x, const float* mean_invstd, const float* gamma,
+                         const float* beta, float* sums, T* dx, T* dres, float* dgamma, float* dbeta, int64_t M, int C,
+                         int relu) {
     const int rows_per_block = 256 / (C >> 3);
     int64_t nb = cr_cdiv(M, (int64_t)rows_per_block * 8);
     if (nb > BNB_MAXBLOCKS) nb = BNB_MAXBLOCKS;
     if (nb < 1) nb = 1;
     float* reduced = sums + (size_t)BNB_MAXBLOCKS * 2 * C;
     const size_t shm = sizeof(float) * rows_per_block * 2 * C;
-    if (act_f32)
-        hipLaunchKernelGGL(k_bn_bwd_reduce<float>, dim3((unsigned)nb), dim3(256), shm, ctx->stream, (const float*)dy,
-                           (const float*)out, (const float*)x, mean_invstd, sums, M, C, relu);
-    else
-        hipLaunchKernelGGL(k_bn_bwd_reduce<u16>, dim3((unsigned)nb), dim3(256), shm, ctx->stream, (const u16*)dy,
-                           (const u16*)out, (const u16*)x, mean_invstd, sums, M, C, relu);
+    hipLaunchKernelGGL((k_bn_bwd_reduce<T, MASKX>), dim3((unsigned)nb), dim3(MASKX ? 512 : 256), shm, ctx->stream, dy, out, x, mean_invstd,
+                       gamma, beta, sums, M, C, relu);
     CR_LAUNCH_CHECK();
     if (C % 32 == 0 && nb <= BN_FUSE_ROWS) {
         int64_t chunks = 1024 / (C / 32);
@@ -3853,30 +3941,51 @@ extern "C" int cr_bn_bwd(cr_ctx* ctx, const void* dy, const void* out, const voi
         int64_t ppb = cr_cdiv(M, chunks);
         ppb = (ppb + 63) / 64 * 64;
         const dim3 grid((unsigned)cr_cdiv(M, ppb), (unsigned)(C / 32));
-        if (act_f32)
-            hipLaunchKernelGGL(k_bn_bwd_apply_fused<float>, grid, dim3(256), 0, ctx->stream, (const float*)dy, (const float*)out,
-                               (const float*)x, mean_invstd, gamma, sums, (int)nb, (float*)dx, (float*)dres, dgamma, dbeta, M, C,
-                               relu, (int)ppb);
-        else
-            hipLaunchKernelGGL(k_bn_bwd_apply_fused<u16>, grid, dim3(256), 0, ctx->stream, (const u16*)dy, (const u16*)out,
-                               (const u16*)x, mean_invstd, gamma, sums, (int)nb, (u16*)dx, (u16*)dres, dgamma, dbeta, M, C, relu,
-                               (int)ppb);
+        hipLaunchKernelGGL((k_bn_bwd_apply_fused<T, MASKX>), grid, dim3(256), 0, ctx->stream, dy, out, x, mean_invstd, gamma,
+                           beta, sums, (int)nb, dx, dres, dgamma, dbeta, M, C, relu, (int)ppb);
         CR_LAUNCH_CHECK();
         return CR_OK;
     }
     hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((unsigned)C), dim3(256), 0, ctx->stream, sums, (int)nb, C, reduced, dgamma,
                        dbeta);
     CR_LAUNCH_CHECK();
-    const int64_t total = M * (C >> 3);
-    const unsigned grid = (unsigned)(cr_cdiv(total, 256) < 4096 ? cr_cdiv(total, 256) : 4096);
-    if (act_f32)
-        hipLaunchKernelGGL(k_bn_bwd_apply<float>, dim3(grid), dim3(256), 0, ctx->stream, (const float*)dy, (const float*)out,
-                           (const float*)x, mean_invstd, gamma, reduced, (float*)dx, (float*)dres, M, C, relu);
-    else
-        hipLaunchKernelGGL(k_bn_bwd_apply<u16>, dim3(grid), dim3(256), 0, ctx->stream, (const u16*)dy, (const u16*)out,
-                           (const u16*)x, mean_invstd, gamma, reduced, (u16*)dx, (u16*)dres, M, C, relu);
+    const int64_t total = M * (C >> BNB_VSHIFT);         // threads' items: twice as many, half as large, with MASKX
+    const int64_t cap = MASKX ? 8192 : 4096;
+    const unsigned grid = (unsigned)(cr_cdiv(total, 256) < cap ? cr_cdiv(total, 256) : cap);
+    hipLaunchKernelGGL((k_bn_bwd_apply<T, MASKX>), dim3(grid), dim3(256), 0, ctx->stream, dy, out, x, mean_invstd, gamma, beta,
+                       reduced, dx, dres, M, C, relu);
     CR_LAUNCH_CHECK();
     return CR_OK;
+}
+
+extern "C" int cr_bn_bwd(cr_ctx* ctx, const void* dy, const void* out, const void* x, const float* mean_invstd,
+                         const float* gamma, float* sums, void* dx, void* dres, float* dgamma, float* dbeta,
+                         int64_t M, int C, int relu, int act_f32) {
+    CR_CHECK_ARG(ctx && dy && x && mean_invstd && gamma && sums && dx && dgamma && dbeta, "cr_bn_bwd: NULL pointer");
+    CR_CHECK_ARG(!relu || out, "cr_bn_bwd: relu needs the forward output");
+    CR_CHECK_ARG(M > 0 && C % 8 == 0 && C <= 2048 && 256 % (C >> 3) == 0, "cr_bn_bwd: unsupported C=%d", C);
+    if (act_f32)
+        return bn_bwd_launch<float, false>(ctx, (const float*)dy, (const float*)out, (const float*)x, mean_invstd, gamma, nullptr,
+                                           sums, (float*)dx, (float*)dres, dgamma, dbeta, M, C, relu);
+    return bn_bwd_launch<u16, false>(ctx, (const u16*)dy, (const u16*)out, (const u16*)x, mean_invstd, gamma, nullptr, sums,
+                                     (u16*)dx, (u16*)dres, dgamma, dbeta, M, C, relu);
+}
+
+// cr_bn_bwd + beta: a ReLU layer without a residual (dres == NULL) may pass out == NULL, the mask then comes from x
+extern "C" int cr_bn_bwd_mask(cr_ctx* ctx, const void* dy, const void* out, const void* x, const float* mean_invstd,
+                              const float* gamma, const float* beta, float* sums, void* dx, void* dres, float* dgamma,
+                              float* dbeta, int64_t M, int C, int relu, int act_f32) {
+    CR_CHECK_ARG(ctx && dy && x && mean_invstd && gamma && beta && sums && dx && dgamma && dbeta, "cr_bn_bwd_mask: NULL pointer");
+    CR_CHECK_ARG(!relu || out || !dres, "cr_bn_bwd_mask: a residual layer's relu needs the forward output");
+    CR_CHECK_ARG(M > 0 && C % 8 == 0 && C <= 2048 && 256 % (C >> 3) == 0, "cr_bn_bwd_mask: unsupported C=%d", C);
+    if (relu && !out) {
+        if (act_f32)
+            return bn_bwd_launch<float, true>(ctx, (const float*)dy, nullptr, (const float*)x, mean_invstd, gamma, beta, sums,
+                                              (float*)dx, nullptr, dgamma, dbeta, M, C, relu);
+        return bn_bwd_launch<u16, true>(ctx, (const u16*)dy, nullptr, (const u16*)x, mean_invstd, gamma, beta, sums, (u16*)dx,
+                                        nullptr, dgamma, dbeta, M, C, relu);
+    }
+    return cr_bn_bwd(ctx, dy, out, x, mean_invstd, gamma, sums, dx, dres, dgamma, dbeta, M, C, relu, act_f32);
 }
 
 // ---------------------------------------------------------------------------

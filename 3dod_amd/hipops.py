@@ -442,7 +442,9 @@ class _ConvBN(torch.autograd.Function):
             ctx.frozen = (running_mean, running_var, float(eps))
         ctx.cfg = (k, stride, pad, relu, training, residual is not None)
         ctx.beta_ref = beta
-        ctx.save_for_backward(x, weight, gamma, y_raw, out if relu else None, mi)
+        # a training ReLU layer without a residual: the backward takes the mask from y_raw (cr_bn_bwd_mask), not from out
+        keep_out = relu and not (training and residual is None)
+        ctx.save_for_backward(x, weight, gamma, y_raw, out if keep_out else None, mi)
         return out
 
     @staticmethod
@@ -474,8 +476,12 @@ class _ConvBN(torch.autograd.Function):
             dgamma = torch.zeros((Cout,), dtype=f32, device=dev)
             dbeta = torch.zeros((Cout,), dtype=f32, device=dev)
             ret_g, ret_b = dgamma, dbeta
-        _lib.call("cr_bn_bwd", dout, out, y_raw, mi, gamma.detach(), sums, dx_raw, dres, dgamma, dbeta, M, Cout, int(relu),
-                  _af(x))
+        if relu and not has_res:
+            _lib.call("cr_bn_bwd_mask", dout, None, y_raw, mi, gamma.detach(), ctx.beta_ref.detach(), sums, dx_raw, None, dgamma,
+                      dbeta, M, Cout, 1, _af(x))
+        else:
+            _lib.call("cr_bn_bwd", dout, out, y_raw, mi, gamma.detach(), sums, dx_raw, dres, dgamma, dbeta, M, Cout, int(relu),
+                      _af(x))
         (xslot, xi), (rslot, ri) = ctx.slots
         if rslot is not None and dres is not None:          # the residual's other consumer (a convolution) adds this
             _slot_put(rslot, dres)

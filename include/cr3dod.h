@@ -368,6 +368,12 @@ int cr_bn_fwd(cr_ctx* ctx, const void* x, const float* stats, int nparts, const 
 int cr_bn_bwd(cr_ctx* ctx, const void* dy, const void* out, const void* x, const float* mean_invstd,
               const float* gamma, float* sums, void* dx, void* dres, float* dgamma, float* dbeta, int64_t M,
               int C, int relu, int act_f32);
+/* cr_bn_bwd plus beta.  With relu != 0, out == NULL and dres == NULL (a ReLU layer without a residual) the mask of element
+ * (m, c) is the sign of the value cr_bn_fwd stored, recomputed bit for bit from x, mean_invstd, gamma and beta (in bf16
+ * storage after the store's rounding) -- the forward output is not read.  With out given: exactly cr_bn_bwd. */
+int cr_bn_bwd_mask(cr_ctx* ctx, const void* dy, const void* out, const void* x, const float* mean_invstd,
+                   const float* gamma, const float* beta, float* sums, void* dx, void* dres, float* dgamma,
+                   float* dbeta, int64_t M, int C, int relu, int act_f32);
 /* BatchNorm2d in eval mode with trainable gamma / beta (freeze_bn fine-tuning), backward after the folded forward
  * (cr_fold_bn + cr_conv2d_fwd with bias, residual, ReLU): from dwf (Cout, K) f32 = weight gradient of the folded convolution
  * (cr_conv2d_bwd_weight_bias on g = dout masked by the ReLU) and sg (Cout) = its fused bias gradient, per channel c with

@@ -117,6 +117,11 @@ SIGNATURES = {
     "cr_maxpool3x3s2_fwd": [P, P, P, c_int, c_int, c_int, c_int, c_int],
     "cr_maxpool3x3s2_bwd": [P, P, P, P, c_int, c_int, c_int, c_int, c_int],
     "cr_cube_decode_infer": [P, P, c_int, P, c_int, P, P, P, P, P, c_int, c_int, P, c_int, c_int, P, P],
+    "cr_cube_select_param": [P, P, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, c_int, c_int, P, P, P,
+                             c_int, c_int, P, P],
+    "cr_cube_select_param_bwd": [P, P, c_int, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P,
+                                 c_int, c_int, P, P, P],
+    "cr_cube_decode_infer_param": [P, P, c_int, P, c_int, P, P, P, P, P, c_int, c_int, P, c_int, c_int, P, P, c_int, c_int, P],
     "cr_box3d_overlap": [P, P, P, c_int, c_int, P, P],
     "cr_nonfinite_flag": [P, P, c_int64, P],
     "cr_sgd_step": [P, P, P, P, c_int64, c_float, P, c_float, c_float, c_float, P],

@@ -886,3 +886,404 @@ extern "C" int cr_cube_decode_infer(cr_ctx* ctx, const float* raw, int ld, const
     CR_LAUNCH_CHECK();
     return CR_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Parametrised selection and inference decode: the options of MODEL.ROI_CUBE_HEAD that change the predictor layout or the
+// decode of a selected column.  cr_cube_select / _bwd / cr_cube_decode_infer above stay the default family (6D pose, an
+// uncertainty block, 'exp' dimension priors); these are their counterparts with three more options:
+//   pose_type   0 '6d'          6 columns per class, Gram-Schmidt (rot6d)
+//               1 'quaternion'  4 columns per class, real part first (cube_head.py:183-187): q / copysign(|q|, q0) -- a zero q0
+//                               counts as positive, pytorch3d _copysign -- then pytorch3d quaternion_to_matrix [third-party,
+//                               restated] with two_s = 2 / sum q^2 recomputed on the normalised quaternion
+//               2 'euler'       3 columns per class (cube_head.py:189-190): pytorch3d euler_angles_to_matrix(e, 'XYZ')
+//                               [third-party, restated] = Rx(e0) Ry(e1) Rz(e2), right-handed axis matrices
+//   o_unc < 0   USE_CONFIDENCE 0: the predictor has no uncertainty block.  Forward writes 0 into the u chunk of buf39 (the loss
+//               kernels run with use_conf = 0: factor 1, g_u = 0); backward writes no uncertainty column.
+//   dims_func   0 'exp': the dr chunk is the raw output and the prior chunk the prior mean, as in cr_cube_select
+//               1 'sigmoid' (roi_heads.py:2385-2388): dims = mn + (mx - mn) sigmoid(raw), mn = max(mean - 3 std, 0), mx = mean +
+//                 3 std.  Selection stores r' = log(dims) in the dr chunk and 1 in the prior chunk, so that k_cube_loss forms
+//                 exp(min(r', 5)) * 1 = dims and returns dL/dr' = dL/ddims * dims; the backward selection multiplies by
+//                 (mx - mn) s (1 - s) / dims.  r' <= 5 holds for every dimension below e^5 = 148 m: above that the clip of
+//                 k_cube_loss would cut the gradient, which no prior table of object sizes reaches.  At the other end, a
+//                 dimension that underflows to 0 (mn = 0, raw below about -88) is held at 1e-30 so that its logarithm and its
+//                 gradient (0, as the reference's) stay finite.
+// Inference without confidence: out column 8 is what the reference's score merge reads.  roi_heads.py:2693-2716 takes
+// cube_3D[:, -1]; without the confidence column the last column is the y coordinate of the projected 2D centre times the image
+// ratio (column 7).  A quirk of the reference, reproduced.
+// ---------------------------------------------------------------------------------------------------------------
+#define CUBE_POSE_W_MAX 6                                   // widest pose block per class ('6d')
+#define CUBE_SEL_STAGE (2 + 3 + CUBE_POSE_W_MAX + 1 + 1)    // staged per RoI by the backward selection: dxy, dims, pose, z, u
+
+struct CubeSelP {
+    CubeSel s;
+    int pose_type, dims_func;
+    const float* priors_std;                                // (K,3) next to s.priors (K,3) -- dims_func 1
+};
+
+__device__ __forceinline__ int pose_width(int pose_type) { return pose_type == 0 ? 6 : (pose_type == 1 ? 4 : 3); }
+
+// q (4 raw columns) -> qn = q / copysign(|q|, q0), R = quaternion_to_matrix(qn); returns the signed norm
+__device__ __forceinline__ float quat_decode(const float* q, float* qn, float* R) {
+    const float nrm = sqrtf(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    const float d = q[0] < 0.f ? -nrm : nrm;
+    const float r = q[0] / d, i = q[1] / d, j = q[2] / d, k = q[3] / d;
+    qn[0] = r; qn[1] = i; qn[2] = j; qn[3] = k;
+    const float t = 2.0f / (((r * r + i * i) + j * j) + k * k);
+    R[0] = 1.f - t * (j * j + k * k); R[1] = t * (i * j - k * r); R[2] = t * (i * k + j * r);
+    R[3] = t * (i * j + k * r); R[4] = 1.f - t * (i * i + k * k); R[5] = t * (j * k - i * r);
+    R[6] = t * (i * k - j * r); R[7] = t * (j * k + i * r); R[8] = 1.f - t * (i * i + j * j);
+    return d;
+}
+
+// dL/dR (9) -> dL/dq (4 raw columns): through quaternion_to_matrix (with its own 2 / sum qn^2) and the signed normalisation
+__device__ __forceinline__ void quat_bwd(const float* q, const float* g, float* gq) {
+    float qn[4], R[9];
+    const float d = quat_decode(q, qn, R);
+    const float r = qn[0], i = qn[1], j = qn[2], k = qn[3];
+    const float t = 2.0f / (((r * r + i * i) + j * j) + k * k);
+    // R_m = c_m +- t A_m: dL/dt, then dt/dqn = -t^2 qn
+    const float gt = (((-g[0] * (j * j + k * k) + g[1] * (i * j - k * r)) + (g[2] * (i * k + j * r) + g[3] * (i * j + k * r))) +
+                      ((-g[4] * (i * i + k * k) + g[5] * (j * k - i * r)) + (g[6] * (i * k - j * r) + g[7] * (j * k + i * r)))) -
+                     g[8] * (i * i + j * j);
+    const float tt = t * t * gt;
+    float gn[4];
+    gn[0] = t * (((g[3] - g[1]) * k + (g[2] - g[6]) * j) + (g[7] - g[5]) * i) - tt * r;
+    gn[1] = t * ((((g[1] + g[3]) * j + (g[2] + g[6]) * k) + (g[7] - g[5]) * r) - 2.f * (g[4] + g[8]) * i) - tt * i;
+    gn[2] = t * ((((g[1] + g[3]) * i + (g[5] + g[7]) * k) + (g[2] - g[6]) * r) - 2.f * (g[0] + g[8]) * j) - tt * j;
+    gn[3] = t * ((((g[2] + g[6]) * i + (g[5] + g[7]) * j) + (g[3] - g[1]) * r) - 2.f * (g[0] + g[4]) * k) - tt * k;
+    // qn = q / d, d = +-|q|: dd/dq = qn
+    const float dot = ((gn[0] * r + gn[1] * i) + gn[2] * j) + gn[3] * k;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) gq[m] = (gn[m] - dot * qn[m]) / d;
+}
+
+// e (3 raw columns) -> R = Rx(e0) Ry(e1) Rz(e2); cs = [cx, sx, cy, sy, cz, sz]
+__device__ __forceinline__ void euler_decode(const float* e, float* R, float* cs) {
+    const float cx = cosf(e[0]), sx = sinf(e[0]), cy = cosf(e[1]), sy = sinf(e[1]), cz = cosf(e[2]), sz = sinf(e[2]);
+    R[0] = cy * cz; R[1] = -(cy * sz); R[2] = sy;
+    R[3] = (sx * sy) * cz + cx * sz; R[4] = cx * cz - (sx * sy) * sz; R[5] = -(sx * cy);
+    R[6] = sx * sz - (cx * sy) * cz; R[7] = (cx * sy) * sz + sx * cz; R[8] = cx * cy;
+    cs[0] = cx; cs[1] = sx; cs[2] = cy; cs[3] = sy; cs[4] = cz; cs[5] = sz;
+}
+
+// dL/dR (9) -> dL/de (3): dR/de0 = (0; -row2; row1), dR/de2 = (col1, -col0, 0), dR/de1 written out
+__device__ __forceinline__ void euler_bwd(const float* e, const float* g, float* ge) {
+    float R[9], cs[6];
+    euler_decode(e, R, cs);
+    const float cx = cs[0], sx = cs[1], cy = cs[2], sy = cs[3], cz = cs[4], sz = cs[5];
+    ge[0] = ((g[6] * R[3] + g[7] * R[4]) + g[8] * R[5]) - ((g[3] * R[6] + g[4] * R[7]) + g[5] * R[8]);
+    ge[1] = ((g[0] * (-sy * cz) + g[1] * (sy * sz)) + g[2] * cy) +
+            (((g[3] * (sx * cy * cz) - g[4] * (sx * cy * sz)) + g[5] * (sx * sy)) +
+             ((g[7] * (cx * cy * sz) - g[6] * (cx * cy * cz)) - g[8] * (cx * sy)));
+    ge[2] = ((g[0] * R[1] + g[3] * R[4]) + g[6] * R[7]) - ((g[1] * R[0] + g[4] * R[3]) + g[7] * R[6]);
+}
+
+// the RoI's pose columns -> R
+__device__ __forceinline__ void pose_decode(const float* r, int o_pose, int c, int pose_type, float* R) {
+    if (pose_type == 1) {
+        float q[4], qn[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = r[o_pose + c * 4 + k];
+        quat_decode(q, qn, R);
+    } else if (pose_type == 2) {
+        float e[3], cs[6];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) e[k] = r[o_pose + c * 3 + k];
+        euler_decode(e, R, cs);
+    } else {
+        float a[6], l1, lu;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) a[k] = r[o_pose + c * 6 + k];
+        rot6d(a, R, &l1, &lu);
+    }
+}
+
+// sigmoid dimension prior: dims = mn + (mx - mn) sigmoid(raw); *dd = d dims / d raw.  The training selection keeps log(dims):
+// with mn = 0 a raw output below about -88 underflows the sigmoid to 0, so the value it stores is held at DIMS_TINY (log finite)
+// and the backward divides by at least that: the gradient there is 0 / DIMS_TINY = 0, as the reference's.
+#define DIMS_TINY 1e-30f
+__device__ __forceinline__ float dims_sigmoid(float raw, float mean, float sd, float* dd) {
+    const float mn = fmaxf(mean - 3.f * sd, 0.f), mx = mean + 3.f * sd, sg = 1.f / (1.f + expf(-raw));
+    if (dd) *dd = (mx - mn) * sg * (1.f - sg);
+    return mn + (mx - mn) * sg;
+}
+
+// k_cube_select with the three options; norm (3, n) as k_cube_select_norm writes it, or NULL
+__global__ __launch_bounds__(64) void k_cube_select_param(CubeSelP pp, float* __restrict__ buf, unsigned char* __restrict__ validf,
+                                                          int* __restrict__ clsc, float* __restrict__ norm) {
+    const CubeSel& p = pp.s;
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= p.n) return;
+    const int b = i / p.kf, j = i - b * p.kf;
+    const size_t bs = (size_t)b * p.S + j;
+    const int64_t c0 = p.cls[bs];
+    const bool v = p.valid[bs] && c0 >= 0 && c0 < p.K;
+    const int c = (int)(c0 < 0 ? 0 : (c0 >= p.K ? p.K - 1 : c0));
+    validf[i] = v ? 1 : 0;
+    clsc[i] = c;
+    const float* r = p.raw + (size_t)i * p.ld;
+    const size_t n = p.n;
+    float* o = buf;
+    o[CUBE_OFF[0] * n + i * 2] = r[p.o_d2 + c * 2]; o[CUBE_OFF[0] * n + i * 2 + 1] = r[p.o_d2 + c * 2 + 1];
+    const int bin = z_bin(p.z_scales, p.boxes, p.bins, i, c);
+    const int cz = p.o_z + bin * p.K + c;
+    float mu = 0.f, sd = 1.f;
+    if (p.z_type == 3) { mu = p.z_stats[(c * p.bins + bin) * 2]; sd = p.z_stats[(c * p.bins + bin) * 2 + 1]; }
+    o[CUBE_OFF[1] * n + i] = z_decode(r[cz], p.z_type, nullptr, mu, sd);
+    if (norm) { norm[i] = r[cz]; norm[n + i] = mu; norm[2 * n + i] = sd; }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float x = r[p.o_dims + c * 3 + k];
+        const bool sg = pp.dims_func == 1;
+        o[CUBE_OFF[2] * n + i * 3 + k] = sg ? logf(fmaxf(dims_sigmoid(x, p.priors[c * 3 + k], pp.priors_std[c * 3 + k], nullptr), DIMS_TINY)) : x;
+        o[CUBE_OFF[7] * n + i * 3 + k] = (sg || !p.priors) ? 1.f : p.priors[c * 3 + k];
+    }
+    float R[9];
+    pose_decode(r, p.o_pose, c, pp.pose_type, R);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) o[CUBE_OFF[3] * n + i * 9 + k] = R[k];
+    o[CUBE_OFF[4] * n + i] = p.o_unc >= 0 ? fmaxf(r[p.o_unc + c], 0.01f) : 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[CUBE_OFF[5] * n + i * 4 + k] = p.meta[b * 5 + k];
+    o[CUBE_OFF[6] * n + i] = p.meta[b * 5 + 4];
+    int64_t gi = p.gt_idx[bs];
+    gi = gi < 0 ? 0 : (gi >= p.G ? p.G - 1 : gi);
+    const float* g3 = p.gt3d + ((size_t)b * p.G + gi) * 9;
+    const float safe[6] = {256.f, 256.f, 5.f, 1.f, 1.f, 1.f};      // a unit cube 5 m in front of the camera
+    o[CUBE_OFF[8] * n + i * 2] = v ? g3[0] : safe[0]; o[CUBE_OFF[8] * n + i * 2 + 1] = v ? g3[1] : safe[1];
+    o[CUBE_OFF[9] * n + i] = v ? g3[2] : safe[2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[CUBE_OFF[10] * n + i * 3 + k] = v ? g3[3 + k] : safe[3 + k];
+    const float* gp = p.gtpose + ((size_t)b * p.G + gi) * 9;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) o[CUBE_OFF[11] * n + i * 9 + k] = gp[k];
+}
+
+// one wave per RoI, as k_cube_select_bwd: lane 0 back-propagates to the selected predictor outputs -- staged as
+// [dxy 2 | dims 3 | pose pw | z | u] -- and the wave writes the dense row.  g_zraw (n) or NULL: the non-disentangled z term's
+// gradient w.r.t. the raw depth, added to the depth column (what k_cube_select_bwd_zraw does in a launch of its own).
+__global__ __launch_bounds__(64) void k_cube_select_param_bwd(CubeSelP pp, const unsigned char* __restrict__ validf,
+                                                              const int* __restrict__ clsc, const float* __restrict__ g_dxy,
+                                                              const float* __restrict__ g_zr, const float* __restrict__ g_dr,
+                                                              const float* __restrict__ g_Ra, const float* __restrict__ g_u,
+                                                              const float* __restrict__ g_usel, const float* __restrict__ g_zraw,
+                                                              float* __restrict__ g_raw) {
+    __shared__ float s[CUBE_SEL_STAGE];
+    const CubeSel& p = pp.s;
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const int c = clsc[i];
+    const bool v = validf[i] != 0;
+    const float* r = p.raw + (size_t)i * p.ld;
+    const int pw = pose_width(pp.pose_type);
+    const int bin = z_bin(p.z_scales, p.boxes, p.bins, i, c);
+    const int zcol = p.o_z + bin * p.K + c;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < CUBE_SEL_STAGE; ++k) s[k] = 0.f;
+        if (v) {
+            s[0] = g_dxy[i * 2]; s[1] = g_dxy[i * 2 + 1];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                float f = 1.f;
+                if (pp.dims_func == 1) {
+                    float dd;
+                    const float dims = dims_sigmoid(r[p.o_dims + c * 3 + k], p.priors[c * 3 + k], pp.priors_std[c * 3 + k], &dd);
+                    f = dd / fmaxf(dims, DIMS_TINY);
+                }
+                s[2 + k] = g_dr[i * 3 + k] * f;
+            }
+            const float* gR = g_Ra + (size_t)i * 9;
+            if (pp.pose_type == 1) {
+                float q[4], gq[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) q[k] = r[p.o_pose + c * 4 + k];
+                quat_bwd(q, gR, gq);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) s[5 + k] = gq[k];
+            } else if (pp.pose_type == 2) {
+                float e[3], ge[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) e[k] = r[p.o_pose + c * 3 + k];
+                euler_bwd(e, gR, ge);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) s[5 + k] = ge[k];
+            } else {
+                // the Gram-Schmidt backward of k_cube_select_bwd, whose device code is pinned and therefore not shared: a change
+                // to either copy goes into both.  No test compares the two copies' gradients to each other; tests/test_gpu_cube_params.py
+                // holds each to the float64 definition at 4 x the float32 floor and compares their zero patterns and copied chunks
+                float a[6], R[9], l1, lu;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) a[k] = r[p.o_pose + c * 6 + k];
+                rot6d(a, R, &l1, &lu);
+                const float* b1 = R; const float* b2 = R + 3;
+                // b3 = b1 x b2
+                float gb1[3] = {gR[0] + (b2[1] * gR[8] - b2[2] * gR[7]), gR[1] + (b2[2] * gR[6] - b2[0] * gR[8]),
+                                gR[2] + (b2[0] * gR[7] - b2[1] * gR[6])};
+                float gb2[3] = {gR[3] + (gR[7] * b1[2] - gR[8] * b1[1]), gR[4] + (gR[8] * b1[0] - gR[6] * b1[2]),
+                                gR[5] + (gR[6] * b1[1] - gR[7] * b1[0])};
+                // b2 = u / |u|
+                const float dot2 = gb2[0] * b2[0] + gb2[1] * b2[1] + gb2[2] * b2[2];
+                float gu[3] = {(gb2[0] - dot2 * b2[0]) / lu, (gb2[1] - dot2 * b2[1]) / lu, (gb2[2] - dot2 * b2[2]) / lu};
+                // u = a2 - d b1, d = b1 . a2
+                const float d = b1[0] * a[3] + b1[1] * a[4] + b1[2] * a[5];
+                const float gd = -(gu[0] * b1[0] + gu[1] * b1[1] + gu[2] * b1[2]);
+                float ga2[3] = {gu[0] + gd * b1[0], gu[1] + gd * b1[1], gu[2] + gd * b1[2]};
+#pragma unroll
+                for (int k = 0; k < 3; ++k) gb1[k] += -d * gu[k] + gd * a[3 + k];
+                // b1 = a1 / |a1|
+                const float dot1 = gb1[0] * b1[0] + gb1[1] * b1[1] + gb1[2] * b1[2];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { s[5 + k] = (gb1[k] - dot1 * b1[k]) / l1; s[8 + k] = ga2[k]; }
+            }
+            float mu = 0.f, sd = 0.f, dz;
+            if (p.z_type == 3) { mu = p.z_stats[(c * p.bins + bin) * 2]; sd = p.z_stats[(c * p.bins + bin) * 2 + 1]; }
+            z_decode(r[zcol], p.z_type, &dz, mu, sd);
+            s[CUBE_SEL_STAGE - 2] = g_zr[i] * dz + (g_zraw ? g_zraw[i] : 0.f);
+            if (p.o_unc >= 0)                    // clip(0.01) passes the gradient where raw >= 0.01
+                s[CUBE_SEL_STAGE - 1] = r[p.o_unc + c] >= 0.01f ? g_u[i] + (g_usel ? g_usel[i] : 0.f) : 0.f;
+        }
+    }
+    __syncthreads();
+    float* g = g_raw + (size_t)i * p.ld;
+    for (int col = lane; col < p.ld; col += 64) {
+        float val = 0.f;
+        int e;
+        if ((e = col - (p.o_d2 + c * 2)) >= 0 && e < 2) val = s[e];
+        else if ((e = col - (p.o_dims + c * 3)) >= 0 && e < 3) val = s[2 + e];
+        else if ((e = col - (p.o_pose + c * pw)) >= 0 && e < pw) val = s[5 + e];
+        else if (col == zcol) val = s[CUBE_SEL_STAGE - 2];
+        else if (p.o_unc >= 0 && col == p.o_unc + c) val = s[CUBE_SEL_STAGE - 1];
+        g[col] = val;
+    }
+}
+
+// the options and the layout against the row stride: every block [offset, offset + width * K) lies inside a row
+static int cube_param_args(CubeSelP& pp, const char* who, const float* raw, int ld, const int* layout5, int K, int z_type, int bins,
+                           const float* z_scales, const float* z_stats, const float* boxes, int pose_type, int dims_func,
+                           const float* priors, const float* priors_std) {
+    CR_CHECK_ARG(raw && layout5 && K > 0 && bins >= 1 && ld > 0, "%s: bad sizes", who);
+    CR_CHECK_ARG(pose_type >= 0 && pose_type <= 2, "%s: pose_type %d (0 6d, 1 quaternion, 2 euler)", who, pose_type);
+    CR_CHECK_ARG(dims_func == 0 || (dims_func == 1 && priors && priors_std),
+                 "%s: dims_func %d (0 exp, 1 sigmoid with the prior means and standard deviations)", who, dims_func);
+    CR_CHECK_ARG(z_type >= 0 && z_type <= 3, "%s: z_type %d (0 direct, 1 sigmoid, 2 log, 3 clusters)", who, z_type);
+    CR_CHECK_ARG(bins == 1 || (z_scales && boxes), "%s: CLUSTER_BINS > 1 needs the scale centres and the RoI boxes", who);
+    CR_CHECK_ARG(z_type != 3 || (bins > 1 && z_stats), "%s: Z_TYPE 'clusters' needs CLUSTER_BINS > 1 and the depth statistics", who);
+    const int pw = pose_type == 0 ? 6 : (pose_type == 1 ? 4 : 3);
+    const int64_t K64 = K;
+    CR_CHECK_ARG(layout5[0] >= 0 && layout5[0] + 2 * K64 <= ld && layout5[1] >= 0 && layout5[1] + 3 * K64 <= ld &&
+                     layout5[2] >= 0 && layout5[2] + pw * K64 <= ld && layout5[3] >= 0 && layout5[3] + bins * K64 <= ld &&
+                     (layout5[4] < 0 || layout5[4] + K64 <= ld),
+                 "%s: the predictor layout does not fit a row of %d columns", who, ld);
+    pp = CubeSelP{};
+    CubeSel& p = pp.s;
+    p.raw = raw; p.ld = ld; p.o_d2 = layout5[0]; p.o_dims = layout5[1]; p.o_pose = layout5[2]; p.o_z = layout5[3];
+    p.o_unc = layout5[4] < 0 ? -1 : layout5[4]; p.K = K; p.priors = priors; p.z_type = z_type; p.bins = bins;
+    p.z_scales = z_scales; p.z_stats = z_stats; p.boxes = boxes;
+    pp.pose_type = pose_type; pp.dims_func = dims_func; pp.priors_std = priors_std;
+    return CR_OK;
+}
+
+extern "C" int cr_cube_select_param(cr_ctx* ctx, const float* raw, int ld, const int* layout5, int K, const int64_t* cls,
+                                    const unsigned char* valid, const int64_t* gt_idx, int B, int S, int kf, int G,
+                                    const float* gt3d, const float* gtpose, const float* priors, const float* meta, float* buf39,
+                                    unsigned char* validf, int* clsc, int z_type, int bins, const float* z_scales,
+                                    const float* z_stats, const float* boxes, int pose_type, int dims_func,
+                                    const float* priors_std, float* norm3) {
+    CR_CHECK_ARG(ctx && buf39 && validf && clsc && cls && valid && gt_idx && gt3d && gtpose && meta, "cr_cube_select_param: NULL pointer");
+    CR_CHECK_ARG(B > 0 && kf > 0 && kf <= S && G > 0, "cr_cube_select_param: bad sizes");
+    CubeSelP pp;
+    int rc = cube_param_args(pp, "cr_cube_select_param", raw, ld, layout5, K, z_type, bins, z_scales, z_stats, boxes, pose_type,
+                             dims_func, priors, priors_std);
+    if (rc) return rc;
+    CubeSel& p = pp.s;
+    p.cls = cls; p.valid = valid; p.gt_idx = gt_idx; p.S = S; p.kf = kf; p.G = G; p.n = B * kf;
+    p.gt3d = gt3d; p.gtpose = gtpose; p.meta = meta;
+    hipLaunchKernelGGL(k_cube_select_param, dim3((unsigned)cr_cdiv(p.n, 64)), dim3(64), 0, ctx->stream, pp, buf39, validf, clsc,
+                       norm3);
+    CR_LAUNCH_CHECK();
+    return CR_OK;
+}
+
+extern "C" int cr_cube_select_param_bwd(cr_ctx* ctx, const float* raw, int ld, const int* layout5, int K, int B, int kf,
+                                        const unsigned char* validf, const int* clsc, const float* g_dxy, const float* g_zr,
+                                        const float* g_dr, const float* g_Ra, const float* g_u, const float* g_usel,
+                                        float* g_raw, int z_type, int bins, const float* z_scales, const float* z_stats,
+                                        const float* boxes, int pose_type, int dims_func, const float* priors,
+                                        const float* priors_std, const float* g_zraw) {
+    CR_CHECK_ARG(ctx && validf && clsc && g_dxy && g_zr && g_dr && g_Ra && g_raw && B >= 0 && kf >= 0,
+                 "cr_cube_select_param_bwd: NULL pointer");
+    CR_CHECK_ARG(layout5 && (layout5[4] < 0 || g_u), "cr_cube_select_param_bwd: an uncertainty block needs g_u");
+    CubeSelP pp;
+    int rc = cube_param_args(pp, "cr_cube_select_param_bwd", raw, ld, layout5, K, z_type, bins, z_scales, z_stats, boxes,
+                             pose_type, dims_func, priors, priors_std);
+    if (rc) return rc;
+    pp.s.kf = kf; pp.s.n = B * kf;
+    if (pp.s.n == 0) return CR_OK;
+    hipLaunchKernelGGL(k_cube_select_param_bwd, dim3(pp.s.n), dim3(64), 0, ctx->stream, pp, validf, clsc, g_dxy, g_zr, g_dr, g_Ra,
+                       g_u, g_usel, g_zraw, g_raw);
+    CR_LAUNCH_CHECK();
+    return CR_OK;
+}
+
+// k_cube_decode_infer with the three options: same meta (B,6), img (n), out (n,42).  Without an uncertainty block column 8 =
+// column 7 (see the section comment: the reference's score merge reads the last column of cube_3D).
+__global__ __launch_bounds__(64) void k_cube_decode_infer_param(CubeSelP pp, const int64_t* __restrict__ cls,
+                                                                const int* __restrict__ img, const float* __restrict__ meta,
+                                                                int n, int allocentric, float* __restrict__ out) {
+    const CubeSel& p = pp.s;
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t c0 = cls[i];
+    const int c = (int)(c0 < 0 ? 0 : (c0 >= p.K ? p.K - 1 : c0));
+    const float* r = p.raw + (size_t)i * p.ld;
+    const float* m = meta + (size_t)img[i] * 6;
+    const float K4[4] = {m[0], m[1], m[2], m[3]};
+    const float* sb = p.boxes + (size_t)i * 4;
+    const float sw = sb[2] - sb[0], sh = sb[3] - sb[1];
+    const float cux = (sb[0] + 0.5f * sw) + sw * r[p.o_d2 + c * 2], cuy = (sb[1] + 0.5f * sh) + sh * r[p.o_d2 + c * 2 + 1];
+    float dims[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float x = r[p.o_dims + c * 3 + k];
+        dims[k] = pp.dims_func == 1 ? dims_sigmoid(x, p.priors[c * 3 + k], pp.priors_std[c * 3 + k], nullptr)
+                                    : expf(fminf(x, 5.0f)) * (p.priors ? p.priors[c * 3 + k] : 1.f);
+    }
+    float Ra[9], R[9], M[9];
+    pose_decode(r, p.o_pose, c, pp.pose_type, Ra);
+    const bool rot = allocentric ? ray_rotation(cux, cuy, K4, M) : false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+            R[a * 3 + q] = rot ? (M[a * 3] * Ra[q] + M[a * 3 + 1] * Ra[3 + q]) + M[a * 3 + 2] * Ra[6 + q] : Ra[a * 3 + q];
+    const float z = z_of(r, p.o_z, p.K, c, i, p.z_type, p.bins, p.z_scales, p.z_stats, p.boxes, nullptr, nullptr) * m[4];
+    const float ctr[3] = {z * (cux - K4[2]) / K4[0], z * (cuy - K4[3]) / K4[1], z};
+    float* o = out + (size_t)i * 42;
+    o[0] = ctr[0]; o[1] = ctr[1]; o[2] = ctr[2];
+    o[3] = dims[0]; o[4] = dims[1]; o[5] = dims[2];
+    o[6] = cux * m[5]; o[7] = cuy * m[5];
+    o[8] = p.o_unc >= 0 ? expf(-fmaxf(r[p.o_unc + c], 0.01f)) : cuy * m[5];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) o[9 + k] = R[k];
+    float P[8][3];
+    corners(ctr, dims, R, P);
+#pragma unroll
+    for (int v = 0; v < 8; ++v) { o[18 + v * 3] = P[v][0]; o[19 + v * 3] = P[v][1]; o[20 + v * 3] = P[v][2]; }
+}
+
+extern "C" int cr_cube_decode_infer_param(cr_ctx* ctx, const float* raw, int ld, const int* layout5, int K, const int64_t* cls,
+                                          const int* img, const float* boxes, const float* meta6, const float* priors, int n,
+                                          int allocentric, float* out42, int z_type, int bins, const float* z_scales,
+                                          const float* z_stats, int pose_type, int dims_func, const float* priors_std) {
+    CR_CHECK_ARG(ctx && n >= 0, "cr_cube_decode_infer_param: bad args");
+    if (n == 0) return CR_OK;
+    CR_CHECK_ARG(cls && img && boxes && meta6 && out42, "cr_cube_decode_infer_param: NULL pointer");
+    CubeSelP pp;
+    int rc = cube_param_args(pp, "cr_cube_decode_infer_param", raw, ld, layout5, K, z_type, bins, z_scales, z_stats, boxes,
+                             pose_type, dims_func, priors, priors_std);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_cube_decode_infer_param, dim3((unsigned)cr_cdiv(n, 64)), dim3(64), 0, ctx->stream, pp, cls, img, meta6, n,
+                       allocentric, out42);
+    CR_LAUNCH_CHECK();
+    return CR_OK;
+}

@@ -322,15 +322,16 @@ def cube_head_losses(rh, features, samp, pred_boxes, gt: GTBatch, meta, pooled=N
         pooled = pool_roi_features(rh, features, samp)[1]
     cube_features = pooled.flatten(1)
     raw, layout = rh.cube_head.forward_fused(cube_features)
-    assert rh.use_confidence > 0 and rh.dims_priors_func == "exp"
     priors = rh.priors_dims_per_cat.detach()[0, :, 0, :].contiguous() if rh.dims_priors_enabled else None
     # DISENTANGLED_LOSS False is passed only when set: the CPU stand-in of this op (oracle/cpu_backend.py) states the default
     # family and has no such argument, so it raises instead of computing the wrong loss
     family = {} if rh.disentangled_loss else {"disentangled": False}
+    family.update(rh.cube_options())         # POSE_TYPE / USE_CONFIDENCE 0 / DIMS_PRIORS_FUNC, likewise only off their defaults
+    use_conf = family.pop("use_conf", True)
     L, u_sel, dec, buf, validf = ops.cube_head_loss(raw, layout, K, samp["classes"], samp["valid"], samp["gt_idx"], kf,
                                                     gt.boxes3D, gt.poses, priors, meta, boxes.reshape(n, 4),
                                                     allocentric=rh.allocentric_pose, chamfer_pose=rh.chamfer_pose,
-                                                    use_conf=True, joint=rh.loss_w_joint > 0, z_cfg=rh.z_cfg(), **family)
+                                                    use_conf=use_conf, joint=rh.loss_w_joint > 0, z_cfg=rh.z_cfg(), **family)
     red, stats = ops.cube_reduce(L, u_sel, buf, dec, validf, inverse_z=bool(rh.inverse_z_weight))
     p = "Cube/"
     w3 = rh.loss_w_3d
@@ -342,7 +343,9 @@ def cube_head_losses(rh, features, samp, pred_boxes, gt: GTBatch, meta, pooled=N
     if wv is None:
         wv = _WVEC[wkey] = torch.tensor(wkey[:6], dtype=torch.float32, device=red.device)
     scaled = (red * wv).unbind(0)
-    losses = {p + "uncert": scaled[5], p + "loss_xy": scaled[1], p + "loss_z": scaled[2], p + "loss_pose": scaled[3]}
+    losses = {p + "loss_xy": scaled[1], p + "loss_z": scaled[2], p + "loss_pose": scaled[3]}
+    if use_conf:                             # roi_heads.py:2632-2651: no uncertainty term and no Cube/conf without confidence
+        losses = {p + "uncert": scaled[5], **losses}
     if rh.loss_w_dims > 0:
         losses[p + "loss_dims"] = scaled[0]
     if rh.loss_w_joint > 0:
@@ -351,7 +354,8 @@ def cube_head_losses(rh, features, samp, pred_boxes, gt: GTBatch, meta, pooled=N
     storage.put_scalar(p + "z_error", stats[0], smoothing_hint=False)
     storage.put_scalar(p + "dims_error", stats[1], smoothing_hint=False)
     storage.put_scalar(p + "xy_error", stats[2], smoothing_hint=False)
-    storage.put_scalar(p + "conf", stats[3], smoothing_hint=False)
+    if use_conf:
+        storage.put_scalar(p + "conf", stats[3], smoothing_hint=False)
     return losses
 
 
@@ -383,14 +387,15 @@ _WEAK_PRIOR_NAN = {}
 
 
 def weak_fusable(rh, kf, dev, masks=None):
-    """whether ops.weak_cube_loss covers this head's configuration: the loss set, uncertainty weighting on, 'exp' dimension
-    priors, at most ops.WEAK_MAX_SLOTS foreground slots per image, no test hook installed (the hooks are CPU restatements of
+    """whether ops.weak_cube_loss covers this head's configuration: the loss set, uncertainty weighting on, the 6D pose, 'exp'
+    dimension priors, at most ops.WEAK_MAX_SLOTS foreground slots per image, no test hook installed (the hooks are CPU restatements of
     single kernels for the tensor composition); CR_WEAK_FUSED=0 selects the composition for comparisons."""
     import os
     if os.environ.get("CR_WEAK_FUSED", "1") == "0" or dev.type != "cuda":
         return False
     hooks = (rh._median_fn, rh._plane_cls, rh._ransac_triples, rh._hull_fn, rh._focal_fn)
     return (set(rh.loss_functions) <= _WEAK_FUSED_LOSSES and rh.use_confidence > 0 and kf <= ops.WEAK_MAX_SLOTS
+            and rh.pose_type == "6d"
             and (not rh.dims_priors_enabled or rh.dims_priors_func == "exp") and all(h is None for h in hooks))
 
 

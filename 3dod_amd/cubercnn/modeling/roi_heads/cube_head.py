@@ -11,7 +11,8 @@ import torch.nn.functional as F
 
 from ....d2lite import Registry, ShapeSpec
 from .... import hipops as ops
-from ...util.math_util import rotation_6d_to_matrix
+from ....hipops import POSE_WIDTH
+from ...util.math_util import rotation_6d_to_matrix, quaternion_pose_to_matrix, euler_angles_to_matrix
 from ..backbone.fpn import c2_xavier_fill
 
 ROI_CUBE_HEAD_REGISTRY = Registry("ROI_CUBE_HEAD")
@@ -29,6 +30,8 @@ class CubeHead(nn.Module):
         super().__init__()
         self.num_classes = cfg.MODEL.ROI_HEADS.NUM_CLASSES
         self.use_conf = cfg.MODEL.ROI_CUBE_HEAD.USE_CONFIDENCE
+        if self.use_conf < 0:                            # (the predictor exists iff USE_CONFIDENCE > 0, here and in ROIHeads3D)
+            raise ValueError("USE_CONFIDENCE is the weight of the uncertainty term: >= 0, got {}".format(self.use_conf))
         self.z_type = cfg.MODEL.ROI_CUBE_HEAD.Z_TYPE
         self.pose_type = cfg.MODEL.ROI_CUBE_HEAD.POSE_TYPE
         self.cluster_bins = cfg.MODEL.ROI_CUBE_HEAD.CLUSTER_BINS
@@ -68,10 +71,9 @@ class CubeHead(nn.Module):
         self.bbox_3D_center_deltas = nn.Linear(self._output_size, self.num_classes * 2)
         nn.init.normal_(self.bbox_3D_center_deltas.weight, std=0.001)
         nn.init.constant_(self.bbox_3D_center_deltas.bias, 0)
-        if self.pose_type == '6d':
-            self.bbox_3D_pose = nn.Linear(self._output_size, self.num_classes * 6)
-        else:
+        if self.pose_type not in POSE_WIDTH:         # '6d' 6, 'quaternion' 4, 'euler' 3 outputs per class (cube_head.py:125-135)
             raise ValueError('Cuboid pose type {} is not recognized'.format(self.pose_type))
+        self.bbox_3D_pose = nn.Linear(self._output_size, self.num_classes * POSE_WIDTH[self.pose_type])
         nn.init.normal_(self.bbox_3D_pose.weight, std=0.001)
         nn.init.constant_(self.bbox_3D_pose.bias, 0)
         self.bbox_3D_center_depth = nn.Linear(self._output_size, self.num_classes * max(1, self.cluster_bins))    # [bin][class] (cube_head.py:141,196-197)
@@ -90,7 +92,7 @@ class CubeHead(nn.Module):
         return h
 
     def _separate(self, x):
-        """SHARED_FC = False (cube_head.py:170-178): every predictor on its own trunk -> [deltas, dims, pose6, z, (uncert)]"""
+        """SHARED_FC = False (cube_head.py:170-178): every predictor on its own trunk -> [deltas, dims, pose, z, (uncert)]"""
         pairs = [(self.feature_generator_XY, self.bbox_3D_center_deltas), (self.feature_generator_dims, self.bbox_3D_dims),
                  (self.feature_generator_pose, self.bbox_3D_pose), (self.feature_generator_Z, self.bbox_3D_center_depth)]
         if self.use_conf:
@@ -115,7 +117,12 @@ class CubeHead(nn.Module):
             outs = [t.contiguous() for t in self._separate(x)]
         box_2d_deltas, box_dims, box_pose, box_z = outs[:4]
         box_uncert = outs[4].clip(0.01) if self.use_conf else None
-        box_pose = rotation_6d_to_matrix(box_pose.view(-1, 6))
+        if self.pose_type == '6d':                       # cube_head.py:180-190
+            box_pose = rotation_6d_to_matrix(box_pose.view(-1, 6))
+        elif self.pose_type == 'quaternion':
+            box_pose = quaternion_pose_to_matrix(box_pose.view(-1, 4))
+        else:
+            box_pose = euler_angles_to_matrix(box_pose.view(-1, 3), 'XYZ')
         box_2d_deltas = box_2d_deltas.view(n, self.num_classes, 2)
         box_dims = box_dims.view(n, self.num_classes, 3)
         box_pose = box_pose.view(n, self.num_classes, 3, 3)
@@ -124,20 +131,24 @@ class CubeHead(nn.Module):
 
 
 def _forward_fused(self, x):
-    """training form for the static-shape path: the five predictors as ONE GEMM.  Returns (raw (n, 13K) f32, layout) with
-    layout = column offsets of [deltas 2K, dims 3K, pose6d 6K, z K, uncert K]; the per-class gather, the 6D -> matrix
+    """training form for the static-shape path: the predictors as ONE GEMM.  Returns (raw (n, ld) f32, layout) with layout =
+    column offsets of [deltas 2K, dims 3K, pose pK, z bins K, uncert K], p = 6 / 4 / 3 for POSE_TYPE '6d' / 'quaternion' /
+    'euler'; with USE_CONFIDENCE 0 there is no uncertainty block and its offset is -1.  The per-class gather, the pose -> matrix
     conversion and the uncertainty clip happen in ops.cube_head_loss (only for each RoI's own class)."""
-    assert self.use_conf
     K = self.num_classes
+    pw = POSE_WIDTH[self.pose_type]
+    o_z = (5 + pw) * K
+    layout = (0, 2 * K, 5 * K, o_z, o_z + max(1, self.cluster_bins) * K if self.use_conf else -1)
     if not self.shared_fc:
-        # per-predictor trunks: five GEMM chains, their outputs laid side by side in the fused layout
-        return torch.cat(self._separate(x), 1), (0, 2 * K, 5 * K, 11 * K, (11 + max(1, self.cluster_bins)) * K)
+        # per-predictor trunks: one GEMM chain each, their outputs laid side by side in the fused layout
+        return torch.cat(self._separate(x), 1), layout
     h = self._trunk(self.feature_generator, x)
-    preds = [self.bbox_3D_center_deltas, self.bbox_3D_dims, self.bbox_3D_pose, self.bbox_3D_center_depth,
-             self.bbox_3D_uncertainty]
+    preds = [self.bbox_3D_center_deltas, self.bbox_3D_dims, self.bbox_3D_pose, self.bbox_3D_center_depth]
+    if self.use_conf:
+        preds.append(self.bbox_3D_uncertainty)
     y, offs = ops.linear_cat(h, [m.weight for m in preds], [m.bias for m in preds])
-    assert tuple(offs[:5]) == (0, 2 * K, 5 * K, 11 * K, (11 + max(1, self.cluster_bins)) * K)
-    return y, tuple(offs[:5])                            # y (n, 13K rounded up to 16) f32; consumers take its row stride
+    assert tuple(offs[:len(preds)]) == layout[:len(preds)]
+    return y, layout                                     # y (n, columns rounded up to 16) f32; consumers take its row stride
 
 
 CubeHead.forward_fused = _forward_fused

@@ -14,6 +14,7 @@ import torch.nn.functional as F
 from ....d2lite import (ROI_HEADS_REGISTRY, ROI_BOX_HEAD_REGISTRY, Boxes, Instances, ShapeSpec, Matcher, cat,
                         pairwise_iou, pairwise_ioa, get_event_storage)
 from .... import hipops as ops
+from ....hipops import pose_type_code, dims_func_code
 from ...util import math_util as util
 from ..backbone.fpn import c2_xavier_fill
 from .cube_head import build_cube_head, fc_nhwc
@@ -170,10 +171,12 @@ class ROIHeads3D(StandardROIHeads):
                              "the reference itself fails (roi_heads.py:2532), so there is nothing to reproduce")
         if self.z_type == 'clusters' and self.cluster_bins <= 1:
             raise ValueError('To use z_type of priors, there must be more than 1 cluster bin')       # roi_heads.py:2044
-        if self.loss_w_3d > 0 and (self.use_confidence <= 0 or (self.dims_priors_enabled and self.dims_priors_func != 'exp')):
-            raise ValueError("the fused 3D-head kernels are built for USE_CONFIDENCE > 0 and DIMS_PRIORS_FUNC 'exp' "
-                             "(configs/Base.yaml); got USE_CONFIDENCE {} / DIMS_PRIORS_FUNC '{}'".format(
-                                 self.use_confidence, self.dims_priors_func))
+        if self.use_confidence < 0:
+            raise ValueError("USE_CONFIDENCE is the weight of the uncertainty term: >= 0, got {}".format(self.use_confidence))
+        if self.loss_w_3d > 0:
+            pose_type_code(self.pose_type)           # raise on values the kernels do not decode, naming the built set
+            if self.dims_priors_enabled:
+                dims_func_code(self.dims_priors_func)
         if self.loss_w_3d > 0:
             in_features = cfg.MODEL.ROI_HEADS.IN_FEATURES
             pooler_scales = tuple(1.0 / input_shape[k].stride for k in in_features)
@@ -198,6 +201,20 @@ class ROIHeads3D(StandardROIHeads):
                     self.priors_z_stats = nn.Parameter(torch.ones(self.num_classes, self.cluster_bins, 2).float())
                 else:
                     self.priors_z_stats = nn.Parameter(torch.cat([torch.FloatTensor(prior[2]).unsqueeze(0) for prior in bins]))
+
+    def cube_options(self):
+        """the ops.cube_head_loss / ops.cube_decode_infer keywords of POSE_TYPE, USE_CONFIDENCE 0 and DIMS_PRIORS_FUNC, each
+        passed only when it differs from its default: the CPU stand-in of these ops (oracle/cpu_backend.py) states the default
+        family and has no such arguments, so it raises instead of computing something else"""
+        opt = {}
+        if self.pose_type != '6d':
+            opt["pose_type"] = self.pose_type
+        if not self.use_confidence > 0:
+            opt["use_conf"] = False
+        if self.dims_priors_enabled and self.dims_priors_func != 'exp':
+            opt["dims_func"] = self.dims_priors_func
+            opt["priors_std"] = self.priors_dims_per_cat.detach()[0, :, 1, :].contiguous()
+        return opt
 
     def z_cfg(self):
         """how a RoI's depth is read from the predictor output (ops.z_config): Z_TYPE, CLUSTER_BINS and the cluster tables"""
@@ -316,7 +333,7 @@ class ROIHeads3D(StandardROIHeads):
             meta6 = torch.tensor(rows, dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
             priors = self.priors_dims_per_cat.detach()[0, :, 0, :].contiguous() if self.dims_priors_enabled else None
             out = ops.cube_decode_infer(raw, layout, K, ocls.reshape(-1), idx, flat.tensor, meta6, priors,
-                                        allocentric=self.allocentric_pose, z_cfg=self.z_cfg()).view(B, D, 42)
+                                        allocentric=self.allocentric_pose, z_cfg=self.z_cfg(), **self.cube_options()).view(B, D, 42)
             score3 = (osc * out[:, :, 8]) ** (1 / 2)
         counts = ocnt.tolist()                                   # the one host wait of the step
         if any(c[1] for c in counts):
@@ -409,8 +426,10 @@ class ROIHeads3D(StandardROIHeads):
 
     def _infer_cube_fused(self, feats, instances, boxes_scaled, boxes, box_classes, Ks, im_current_dims, im_scales_ratio):
         """inference decode + packing (roi_heads.py:2353-2436, 2682-2735) on the fused path: one ROIAlign, the shared
-        FCs + one predictor GEMM, one decode kernel (cr_cube_decode_infer); the torch expressions of _forward_cube stay
-        the CPU / oracle statement of the same arithmetic (tests/test_gpu_model.py compares the two)."""
+        FCs + one predictor GEMM, one decode kernel (cr_cube_decode_infer, or cr_cube_decode_infer_param off the default pose
+        type / confidence / prior function); the torch expressions of _forward_cube stay the CPU / oracle statement of the same
+        arithmetic (tests/test_gpu_model.py compares the two).  Column 8 of the decode is the 3D score factor: exp(-uncertainty),
+        or with USE_CONFIDENCE 0 what the reference's merge reads there, the projected centre's y (roi_heads.py:2693-2716)."""
         dev = feats[0].device
         counts = [len(b) for b in boxes]
         n = sum(counts)
@@ -427,7 +446,7 @@ class ROIHeads3D(StandardROIHeads):
         meta6 = torch.tensor(rows, dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
         priors = self.priors_dims_per_cat.detach()[0, :, 0, :].contiguous() if self.dims_priors_enabled else None
         out = ops.cube_decode_infer(raw, layout, self.num_classes, box_classes, idx, torch.cat([b.tensor for b in boxes]),
-                                    meta6, priors, allocentric=self.allocentric_pose, z_cfg=self.z_cfg())
+                                    meta6, priors, allocentric=self.allocentric_pose, z_cfg=self.z_cfg(), **self.cube_options())
         for inst, o, cls_i in zip(instances, out.split(counts), box_classes.split(counts)):
             m = o.shape[0]
             inst.scores = (inst.scores * o[:, 8]) ** (1 / 2) if inst.has('scores') else o[:, 8]

@@ -85,12 +85,40 @@ def rotation_6d_to_matrix(d6):
 
 
 def quaternion_to_matrix(q):
+    """pytorch3d.transforms.quaternion_to_matrix [third-party, restated]: q (..., 4), real part first."""
     r, i, j, k = torch.unbind(q, -1)
     two_s = 2.0 / (q * q).sum(-1)
     o = torch.stack((1 - two_s * (j * j + k * k), two_s * (i * j - k * r), two_s * (i * k + j * r),
                      two_s * (i * j + k * r), 1 - two_s * (i * i + k * k), two_s * (j * k - i * r),
                      two_s * (i * k - j * r), two_s * (j * k + i * r), 1 - two_s * (i * i + j * j)), -1)
     return o.reshape(q.shape[:-1] + (3, 3))
+
+
+def quaternion_pose_to_matrix(quats):
+    """POSE_TYPE 'quaternion' (cube_head.py:183-187): q (..., 4), real part first, divided by copysign(|q|, q0) -- pytorch3d
+    _copysign [third-party, restated]: the sign flips only where q0 < 0, so a zero q0 counts as positive -- then pytorch3d
+    quaternion_to_matrix [third-party, restated], which forms 2 / sum q^2 again on the normalised quaternion."""
+    norm = torch.sqrt((quats * quats).sum(-1))
+    signed = torch.where(quats[..., 0] < 0, -norm, norm)
+    return quaternion_to_matrix(quats / signed[..., None])
+
+
+def euler_angles_to_matrix(euler_angles, convention="XYZ"):
+    """pytorch3d.transforms.euler_angles_to_matrix [third-party, restated]: the product of the right-handed axis rotations in the
+    order of `convention`; 'XYZ' = Rx(e0) @ Ry(e1) @ Rz(e2)."""
+    if len(convention) != 3 or any(c not in "XYZ" for c in convention) or convention[1] in (convention[0], convention[2]):
+        raise ValueError("Invalid convention {}.".format(convention))
+    mats = []
+    for axis, angle in zip(convention, torch.unbind(euler_angles, -1)):
+        c, s, one, zero = torch.cos(angle), torch.sin(angle), torch.ones_like(angle), torch.zeros_like(angle)
+        if axis == "X":
+            flat = (one, zero, zero, zero, c, -s, zero, s, c)
+        elif axis == "Y":
+            flat = (c, zero, s, zero, one, zero, -s, zero, c)
+        else:
+            flat = (c, -s, zero, s, c, zero, zero, zero, one)
+        mats.append(torch.stack(flat, -1).reshape(angle.shape + (3, 3)))
+    return torch.matmul(torch.matmul(mats[0], mats[1]), mats[2])
 
 
 def axis_angle_to_matrix(axis_angle):

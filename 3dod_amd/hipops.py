@@ -1896,6 +1896,31 @@ def z_type_code(z_type):
     return Z_TYPES[z_type]
 
 
+# MODEL.ROI_CUBE_HEAD.POSE_TYPE values the kernels decode (cube_head.py:180-190) and the columns each takes per class
+POSE_TYPES = {"6d": 0, "quaternion": 1, "euler": 2}
+POSE_WIDTH = {"6d": 6, "quaternion": 4, "euler": 3}
+# MODEL.ROI_CUBE_HEAD.DIMS_PRIORS_FUNC values (roi_heads.py:2385-2390)
+DIMS_FUNCS = {"exp": 0, "sigmoid": 1}
+
+
+def pose_type_code(pose_type):
+    if pose_type not in POSE_TYPES:
+        raise ValueError(f"POSE_TYPE '{pose_type}' is not built (built: {sorted(POSE_TYPES)})")
+    return POSE_TYPES[pose_type]
+
+
+def dims_func_code(dims_func, priors=None, priors_std=None):
+    """code of DIMS_PRIORS_FUNC for the prior tables (K,3) at hand: 'sigmoid' decodes between mean -+ 3 std and needs both;
+    without priors the dimensions are exp(raw) whatever the function says (roi_heads.py:2392-2394) -> 0"""
+    if dims_func not in DIMS_FUNCS:
+        raise ValueError(f"DIMS_PRIORS_FUNC '{dims_func}' is not built (built: {sorted(DIMS_FUNCS)})")
+    if priors is None:
+        return 0
+    if dims_func == "sigmoid" and priors_std is None:
+        raise ValueError("DIMS_PRIORS_FUNC 'sigmoid' needs the standard deviations of the dimension priors (priors_std)")
+    return DIMS_FUNCS[dims_func]
+
+
 def z_config(z_type="direct", bins=1, z_scales=None, z_stats=None):
     """(code, bins, z_scales (K,bins) f32 or None, z_stats (K,bins,2) f32 or None): how a RoI's depth is read from the predictor
     output -- MODEL.ROI_CUBE_HEAD.Z_TYPE / CLUSTER_BINS with the head's priors_z_scales / priors_z_stats (roi_heads.py:2343-2436)"""
@@ -2023,13 +2048,95 @@ class _CubeHeadLossNondis(torch.autograd.Function):
         return (g_raw.to(dt),) + (None,) * 11
 
 
+class _CubeHeadLossParam(torch.autograd.Function):
+    """_CubeHeadLoss / _CubeHeadLossNondis for the options that change the predictor layout or the decode of a selected column
+    (POSE_TYPE 'quaternion' / 'euler', no uncertainty block, DIMS_PRIORS_FUNC 'sigmoid'): cr_cube_select_param / _param_bwd around
+    the same loss kernels.  The selection writes the three `norm` rows of the non-disentangled loss itself and its backward adds
+    the raw-depth gradient, so both families take two launches each way."""
+
+    @staticmethod
+    def forward(ctx, raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors, priors_std, meta, boxes, flags):
+        allocentric, chamfer_pose, use_conf, joint, zc, disentangled, pose_code, dims_code = flags
+        _need_cuda(raw, "cube head output")
+        B, S = cls.shape
+        n = B * kf
+        dev = raw.device
+        raw32 = raw.detach().float().contiguous()
+        rows = 39 if disentangled else 42
+        buf_all = torch.empty((rows * n,), dtype=f32, device=dev)
+        buf, norm = buf_all[:39 * n], (None if disentangled else buf_all[39 * n:])
+        validf = torch.empty((n,), dtype=torch.uint8, device=dev)
+        clsc = torch.empty((n,), dtype=torch.int32, device=dev)
+        lay = (_ct.c_int * 5)(*[int(v) for v in layout])
+        boxes = boxes.float().contiguous()
+        _lib.call("cr_cube_select_param", raw32, raw32.shape[1], lay, int(K), cls.contiguous(),
+                  valid.to(torch.uint8).contiguous(), gt_idx.contiguous(), B, S, int(kf), gt3d.shape[1], gt3d.contiguous(),
+                  gtpose.contiguous(), priors, meta.contiguous(), buf, validf, clsc, zc[0], zc[1], zc[2], zc[3], boxes,
+                  pose_code, dims_code, priors_std, norm)
+        ch, arr = _cube_loss_ins(buf, boxes, n)
+        losses = torch.empty((n, 5), dtype=f32, device=dev)
+        dec = torch.empty((n, 17), dtype=f32, device=dev)
+        if disentangled:
+            _lib.call("cr_cube_loss_fwd", arr, n, allocentric, chamfer_pose, use_conf, joint, losses, dec)
+        else:
+            _lib.call("cr_cube_nondis_fwd", arr, norm, n, allocentric, use_conf, joint, zc[0], losses, dec)
+        ctx.keep = (raw32, buf_all, validf, clsc, boxes, priors, priors_std, tuple(int(v) for v in layout), int(K), B, int(kf), flags,
+                    raw.dtype)
+        ctx.set_materialize_grads(False)       # outputs nobody differentiates arrive as None, not as zero fills
+        ctx.mark_non_differentiable(dec, buf, validf)
+        return losses, ch[4].clone(), dec, buf, validf
+
+    @staticmethod
+    def backward(ctx, gl, g_usel, _gd, _gb, _gv):
+        raw32, buf_all, validf, clsc, boxes, priors, priors_std, layout, K, B, kf, flags, dt = ctx.keep
+        allocentric, chamfer_pose, use_conf, joint, zc, disentangled, pose_code, dims_code = flags
+        n = B * kf
+        buf, norm = buf_all[:39 * n], (None if disentangled else buf_all[39 * n:])
+        _, arr = _cube_loss_ins(buf, boxes, n)
+        glc = gl.contiguous()
+        g_zraw = None
+        if disentangled:
+            g_dxy, g_zr, g_dr, g_Ra, g_u = _cube_grads(n, raw32.device)
+            _lib.call("cr_cube_loss_bwd", arr, n, allocentric, chamfer_pose, use_conf, joint, glc, g_dxy, g_zr, g_dr, g_Ra, g_u)
+        else:
+            g_dxy, g_zr, g_dr, g_Ra, g_u, g_zraw = _cube_grads(n, raw32.device, zraw=True)
+            _lib.call("cr_cube_nondis_bwd", arr, norm, n, allocentric, use_conf, joint, zc[0], glc, g_dxy, g_zr, g_dr, g_Ra, g_u,
+                      g_zraw)
+            if zc[0] == 0:                     # 'direct' has no normalised depth space: its z term went through g_zr
+                g_zraw = None
+        g_raw = torch.empty_like(raw32)
+        lay = (_ct.c_int * 5)(*layout)
+        _lib.call("cr_cube_select_param_bwd", raw32, raw32.shape[1], lay, K, B, kf, validf, clsc, g_dxy, g_zr, g_dr, g_Ra, g_u,
+                  None if g_usel is None else g_usel.contiguous(), g_raw, zc[0], zc[1], zc[2], zc[3], boxes, pose_code, dims_code,
+                  priors, priors_std, g_zraw)
+        return (g_raw.to(dt),) + (None,) * 13
+
+
 def cube_head_loss(raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors, meta, boxes, allocentric=True,
-                   chamfer_pose=True, use_conf=True, joint=True, z_type="direct", z_cfg=None, disentangled=True):
-    """raw (n,13K) fused predictor output; cls/valid/gt_idx (B,S); gt3d (B,G,9); gtpose (B,G,3,3); priors (K,3) or None;
+                   chamfer_pose=True, use_conf=True, joint=True, z_type="direct", z_cfg=None, disentangled=True,
+                   pose_type="6d", dims_func="exp", priors_std=None):
+    """raw (n, ld) fused predictor output (13K columns in the default family); cls/valid/gt_idx (B,S); gt3d (B,G,9); gtpose
+    (B,G,3,3); priors (K,3) or None;
     meta (B,5); boxes (n,4).  -> losses (n,5), u_sel (n), dec (n,17), buf39, validf (n) uint8.
     disentangled=False: the non-disentangled losses of MODEL.ROI_CUBE_HEAD.DISENTANGLED_LOSS False (roi_heads.py:2516-2560);
     `priors` must be None (the reference fails with the dimension priors there, :2532) and `chamfer_pose` plays no part (the
-    pose term is the relative rotation angle, the joint term is L1, :2587-2591)."""
+    pose term is the relative rotation angle, the joint term is L1, :2587-2591).
+    pose_type '6d' | 'quaternion' | 'euler': the pose block of `raw` has 6 / 4 / 3 columns per class (cube_head.py:180-190).
+    use_conf=False: USE_CONFIDENCE 0, `raw` has no uncertainty block (layout[4] is not read); u_sel is 0 and takes no gradient.
+    dims_func 'exp' | 'sigmoid' with priors_std (K,3): DIMS_PRIORS_FUNC (roi_heads.py:2385-2390); only read with `priors`.
+    With the default values of these three the entry points of the default family are launched, as before."""
+    pose_code = pose_type_code(pose_type)
+    dims_code = dims_func_code(dims_func, priors, priors_std)
+    if pose_code != 0 or dims_code != 0 or not use_conf:
+        if not disentangled and priors is not None:
+            raise ValueError("cube_head_loss: the non-disentangled loss is built without dimension priors "
+                             "(DIMS_PRIORS_ENABLED False): the reference fails with them (roi_heads.py:2532)")
+        lay = tuple(int(v) for v in layout[:4]) + (int(layout[4]) if use_conf else -1,)
+        flags = (int(bool(allocentric)), int(bool(chamfer_pose)), int(bool(use_conf)), int(bool(joint)), z_cfg or z_config(z_type),
+                 bool(disentangled), pose_code, dims_code)
+        f = lambda t: None if t is None else t.detach().float().contiguous()
+        return _CubeHeadLossParam.apply(raw, lay, K, cls, valid, gt_idx, kf, gt3d, gtpose.reshape(gtpose.shape[0], -1, 9),
+                                        f(priors), f(priors_std) if dims_code else None, meta, boxes, flags)
     if not disentangled:
         if priors is not None:
             raise ValueError("cube_head_loss: the non-disentangled loss is built without dimension priors "
@@ -2042,14 +2149,27 @@ def cube_head_loss(raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors,
                                priors, meta, boxes, flags)
 
 
-def cube_decode_infer(raw, layout, K, cls, img, boxes, meta6, priors, allocentric=True, z_type="direct", z_cfg=None):
-    """inference decode of the 3D head (no autograd) -> (n,42), see cr_cube_decode_infer."""
+def cube_decode_infer(raw, layout, K, cls, img, boxes, meta6, priors, allocentric=True, z_type="direct", z_cfg=None,
+                      pose_type="6d", use_conf=True, dims_func="exp", priors_std=None):
+    """inference decode of the 3D head (no autograd) -> (n,42), see cr_cube_decode_infer.  pose_type / use_conf / dims_func /
+    priors_std as in cube_head_loss; off their defaults the decode is cr_cube_decode_infer_param.  Without confidence column 8
+    repeats column 7 (the reference's score merge reads the last column of its cube_3D, roi_heads.py:2693-2716)."""
     _need_cuda(raw, "cube head output")
     n = raw.shape[0]
     out = torch.empty((n, 42), dtype=f32, device=raw.device)
     raw32 = raw.detach().float().contiguous()
-    lay = (_ct.c_int * 5)(*[int(v) for v in layout])
     zc = z_cfg or z_config(z_type)
+    pose_code = pose_type_code(pose_type)
+    dims_code = dims_func_code(dims_func, priors, priors_std)
+    if pose_code != 0 or dims_code != 0 or not use_conf:
+        lay = (_ct.c_int * 5)(*([int(v) for v in layout[:4]] + [int(layout[4]) if use_conf else -1]))
+        f = lambda t: None if t is None else t.detach().float().contiguous()
+        _lib.call("cr_cube_decode_infer_param", raw32, raw32.shape[1], lay, int(K), cls.contiguous(),
+                  img.to(torch.int32).contiguous(), boxes.float().contiguous(), meta6.contiguous(), f(priors), n,
+                  int(bool(allocentric)), out, zc[0], zc[1], zc[2], zc[3], pose_code, dims_code,
+                  f(priors_std) if dims_code else None)
+        return out
+    lay = (_ct.c_int * 5)(*[int(v) for v in layout])
     _lib.call("cr_cube_decode_infer", raw32, raw32.shape[1], lay, int(K), cls.contiguous(), img.to(torch.int32).contiguous(),
               boxes.float().contiguous(), meta6.contiguous(), priors, n, int(bool(allocentric)), out, zc[0], zc[1], zc[2],
               zc[3])

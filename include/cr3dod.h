@@ -647,6 +647,41 @@ int cr_cube_decode_infer(cr_ctx* ctx, const float* raw, int ld, const int* layou
                          const int* img, const float* boxes, const float* meta6, const float* priors, int n,
                          int allocentric, float* out42, int z_type, int bins, const float* z_scales, const float* z_stats);
 
+/* ---- MODEL.ROI_CUBE_HEAD.POSE_TYPE 'quaternion' / 'euler', USE_CONFIDENCE 0, DIMS_PRIORS_FUNC 'sigmoid': parametrised
+ * counterparts of cr_cube_select / cr_cube_select_bwd / cr_cube_decode_infer, additive to the entries above (which stay the
+ * default family: 6D pose, an uncertainty block, 'exp' priors).  Same arguments, plus:
+ *   pose_type  0 '6d' (6 columns per class) | 1 'quaternion' (4 columns, real part first: q / copysign(|q|, q0), a zero q0 counts
+ *              as positive, then quaternion_to_matrix; cube_head.py:183-187) | 2 'euler' (3 columns: Rx(e0) Ry(e1) Rz(e2),
+ *              euler_angles_to_matrix(e, 'XYZ'); cube_head.py:189-190).  layout5[2] is the pose block, pose width x K columns.
+ *   layout5[4] < 0: USE_CONFIDENCE 0, the predictor has no uncertainty block.  The u chunk of buf39 is 0 (run the loss kernels
+ *              with use_conf = 0), the backward writes no uncertainty column and reads neither g_u nor g_usel (g_usel may be NULL
+ *              in any case).
+ *   dims_func  0 'exp' | 1 'sigmoid' (roi_heads.py:2385-2388): dims = mn + (mx - mn) sigmoid(raw), mn = max(mean - 3 std, 0),
+ *              mx = mean + 3 std with priors (K,3) the means and priors_std (K,3) the standard deviations, both required.  The dr
+ *              chunk of buf39 then holds log(dims) and the prior chunk 1, so that cr_cube_loss_fwd / _bwd are used as they are
+ *              (exp(min(log dims, 5)) * 1 = dims for every dimension below e^5 = 148 m); the backward multiplies the gradient of
+ *              the dr chunk by (mx - mn) s (1 - s) / dims.
+ * The layout is checked against ld block by block (every block offset + width * K <= ld), not by the 13K rule of cr_cube_select.
+ * norm3 (3*n) or NULL: what cr_cube_select_norm writes, in the same launch.  g_zraw (n) or NULL: added to the depth column, what
+ * cr_cube_select_bwd_zraw does. */
+int cr_cube_select_param(cr_ctx* ctx, const float* raw, int ld, const int* layout5, int K, const int64_t* cls,
+                         const unsigned char* valid, const int64_t* gt_idx, int B, int S, int kf, int G, const float* gt3d,
+                         const float* gtpose, const float* priors, const float* meta, float* buf39, unsigned char* validf,
+                         int* clsc, int z_type, int bins, const float* z_scales, const float* z_stats, const float* boxes,
+                         int pose_type, int dims_func, const float* priors_std, float* norm3);
+int cr_cube_select_param_bwd(cr_ctx* ctx, const float* raw, int ld, const int* layout5, int K, int B, int kf,
+                             const unsigned char* validf, const int* clsc, const float* g_dxy, const float* g_zr,
+                             const float* g_dr, const float* g_Ra, const float* g_u, const float* g_usel, float* g_raw,
+                             int z_type, int bins, const float* z_scales, const float* z_stats, const float* boxes,
+                             int pose_type, int dims_func, const float* priors, const float* priors_std, const float* g_zraw);
+/* out42 as cr_cube_decode_infer.  Without an uncertainty block column 8 repeats column 7: the reference's score merge reads the
+ * LAST column of its cube_3D (roi_heads.py:2693-2716), which without the confidence column is the y coordinate of the projected
+ * 2D centre x ratio.  A quirk of the reference, reproduced. */
+int cr_cube_decode_infer_param(cr_ctx* ctx, const float* raw, int ld, const int* layout5, int K, const int64_t* cls,
+                               const int* img, const float* boxes, const float* meta6, const float* priors, int n,
+                               int allocentric, float* out42, int z_type, int bins, const float* z_scales,
+                               const float* z_stats, int pose_type, int dims_func, const float* priors_std);
+
 /* ---- exact IoU of oriented 3D boxes -----------------------------------------------------------
  * replaces pytorch3d box3d_overlap / _C.iou_box3d [third-party] at ProposalNetwork/utils/utils.py:194-210,
  * cubercnn/evaluation/omni3d_evaluation.py:155, cubercnn/modeling/roi_heads/roi_heads.py:518,526,1563.

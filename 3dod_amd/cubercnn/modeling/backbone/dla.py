@@ -1,7 +1,9 @@
-"""DLA-34 trunk on the HIP conv kernels.  Same module tree (hence the same state-dict keys,
-e.g. `level2.tree1.conv1.weight`) as cubercnn/modeling/backbone/dla.py:40-68,156-321,417-507 of the
+"""The ten DLA trunks on the HIP conv kernels.  Same module tree (hence the same state-dict keys,
+e.g. `level2.tree1.conv1.weight`) as cubercnn/modeling/backbone/dla.py:40-507 of the
 reference; nn.Conv2d / nn.BatchNorm2d are used as PARAMETER CONTAINERS only -- the arithmetic runs in
-cr_conv2d_* / cr_bn_* (NHWC bf16 activations, f32 statistics).  BatchNorm is per-GPU (dla.py:17)."""
+cr_conv2d_* / cr_bn_* (NHWC bf16 activations, f32 statistics).  BatchNorm is per-GPU (dla.py:17).  The grouped 3x3
+convolution of the DLA-X blocks runs in cr_conv2d_grouped_* (csrc/conv_grouped.hip)."""
+import functools
 import math
 
 import torch
@@ -17,11 +19,12 @@ BatchNorm = nn.BatchNorm2d
 
 def _conv_bn(x, conv, bn, relu, residual=None):
     w = conv.weight
-    if w.shape[1] < x.shape[-1]:      # RGB stem: activations carry 8 (bf16) or 4 (f32) channels, 3 real + zeros
+    if conv.groups == 1 and w.shape[1] < x.shape[-1]:      # RGB stem: activations carry 8 (bf16) or 4 (f32) channels, 3 real + zeros
         w = ops.pad_input_channels(w, x.shape[-1])
+    grouped = {"groups": conv.groups} if conv.groups > 1 else {}         # dense layers: the call as it always was
     return ops.conv_bn_act(x, w, bn.weight, bn.bias, bn.running_mean, bn.running_var, stride=conv.stride[0],
                            pad=conv.padding[0], relu=relu, residual=residual, eps=bn.eps, momentum=bn.momentum,
-                           training=bn.training)
+                           training=bn.training, **grouped)
 
 
 class BasicBlock(nn.Module):
@@ -40,6 +43,60 @@ class BasicBlock(nn.Module):
             residual = x
         out = _conv_bn(x, self.conv1, self.bn1, relu=True)
         return _conv_bn(out, self.conv2, self.bn2, relu=True, residual=residual)     # out += residual; relu
+
+
+class Bottleneck(nn.Module):
+    """dla.py:71-109: 1x1 -> 3x3 -> 1x1 with planes // expansion channels in the middle"""
+    expansion = 2
+
+    def __init__(self, inplanes, planes, stride=1, dilation=1):
+        super().__init__()
+        assert dilation == 1
+        bottle_planes = planes // Bottleneck.expansion
+        self.conv1 = nn.Conv2d(inplanes, bottle_planes, kernel_size=1, bias=False)
+        self.bn1 = BatchNorm(bottle_planes)
+        self.conv2 = nn.Conv2d(bottle_planes, bottle_planes, kernel_size=3, stride=stride, padding=dilation, bias=False)
+        self.bn2 = BatchNorm(bottle_planes)
+        self.conv3 = nn.Conv2d(bottle_planes, planes, kernel_size=1, bias=False)
+        self.bn3 = BatchNorm(planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.stride = stride
+
+    def forward(self, x, residual=None):
+        if residual is None:
+            residual = x
+        out = _conv_bn(x, self.conv1, self.bn1, relu=True)
+        out = _conv_bn(out, self.conv2, self.bn2, relu=True)
+        return _conv_bn(out, self.conv3, self.bn3, relu=True, residual=residual)     # out += residual; relu
+
+
+class BottleneckX(nn.Module):
+    """dla.py:112-153: the middle 3x3 convolution is grouped (`cardinality` groups, planes * cardinality // 32 channels).
+    The reference keeps the cardinality in a class attribute that dla102x2 sets to 64 for the rest of the process
+    (dla.py:400-401); here it is an argument of the instance."""
+    expansion = 2
+
+    def __init__(self, inplanes, planes, stride=1, dilation=1, cardinality=32):
+        super().__init__()
+        assert dilation == 1
+        bottle_planes = planes * cardinality // 32
+        self.conv1 = nn.Conv2d(inplanes, bottle_planes, kernel_size=1, bias=False)
+        self.bn1 = BatchNorm(bottle_planes)
+        self.conv2 = nn.Conv2d(bottle_planes, bottle_planes, kernel_size=3, stride=stride, padding=dilation, bias=False,
+                               groups=cardinality)
+        self.bn2 = BatchNorm(bottle_planes)
+        self.conv3 = nn.Conv2d(bottle_planes, planes, kernel_size=1, bias=False)
+        self.bn3 = BatchNorm(planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.stride = stride
+        self.cardinality = cardinality
+
+    def forward(self, x, residual=None):
+        if residual is None:
+            residual = x
+        out = _conv_bn(x, self.conv1, self.bn1, relu=True)
+        out = _conv_bn(out, self.conv2, self.bn2, relu=True)
+        return _conv_bn(out, self.conv3, self.bn3, relu=True, residual=residual)     # out += residual; relu
 
 
 class Root(nn.Module):
@@ -165,13 +222,79 @@ def dla34(pretrained=False, tricks=False, **kwargs):
     return DLA([1, 1, 1, 2, 2, 1], [16, 32, 64, 128, 256, 512], block=BasicBlock, **kwargs)
 
 
+# dla.py:324-415 (no pretrained weights: there is no network here -> random init, as for dla34)
+_SMALL = [16, 32, 64, 64, 128, 256]
+_LARGE = [16, 32, 128, 256, 512, 1024]
+
+
+def _block_x(cardinality):
+    return functools.partial(BottleneckX, cardinality=cardinality)
+
+
+def dla46_c(pretrained=False, **kwargs):
+    return DLA([1, 1, 1, 2, 2, 1], _SMALL, block=Bottleneck, **kwargs)
+
+
+def dla46x_c(pretrained=False, **kwargs):
+    return DLA([1, 1, 1, 2, 2, 1], _SMALL, block=_block_x(32), **kwargs)
+
+
+def dla60x_c(pretrained=False, **kwargs):
+    return DLA([1, 1, 1, 2, 3, 1], _SMALL, block=_block_x(32), **kwargs)
+
+
+def dla60(pretrained=False, tricks=False, **kwargs):
+    return DLA([1, 1, 1, 2, 3, 1], _LARGE, block=Bottleneck, **kwargs)
+
+
+def dla60x(pretrained=False, **kwargs):
+    return DLA([1, 1, 1, 2, 3, 1], _LARGE, block=_block_x(32), **kwargs)
+
+
+def dla102(pretrained=False, tricks=False, **kwargs):
+    return DLA([1, 1, 1, 3, 4, 1], _LARGE, block=Bottleneck, residual_root=True, **kwargs)
+
+
+def dla102x(pretrained=False, **kwargs):
+    return DLA([1, 1, 1, 3, 4, 1], _LARGE, block=_block_x(32), residual_root=True, **kwargs)
+
+
+def dla102x2(pretrained=False, **kwargs):
+    return DLA([1, 1, 1, 3, 4, 1], _LARGE, block=_block_x(64), residual_root=True, **kwargs)
+
+
+def dla169(pretrained=False, **kwargs):
+    return DLA([1, 1, 2, 3, 5, 1], _LARGE, block=Bottleneck, residual_root=True, **kwargs)
+
+
+_CH_34 = {'p2': 64, 'p3': 128, 'p4': 256, 'p5': 512, 'p6': 512}
+_CH_SMALL = {'p2': 64, 'p3': 64, 'p4': 128, 'p5': 256, 'p6': 256}
+_CH_LARGE = {'p2': 128, 'p3': 256, 'p4': 512, 'p5': 1024, 'p6': 1024}
+# MODEL.DLA.TYPE -> (constructor, output channels), dla.py:421-450
+DLA_TYPES = {
+    "dla34": (dla34, _CH_34),
+    "dla46_c": (dla46_c, _CH_SMALL),
+    "dla46x_c": (dla46x_c, _CH_SMALL),
+    "dla60x_c": (dla60x_c, _CH_SMALL),
+    "dla60": (dla60, _CH_LARGE),
+    "dla60x": (dla60x, _CH_LARGE),
+    "dla102": (dla102, _CH_LARGE),
+    "dla102x": (dla102x, _CH_LARGE),
+    "dla102x2": (dla102x2, _CH_LARGE),
+    "dla169": (dla169, _CH_LARGE),
+}
+
+
 class DLABackbone(Backbone):
     def __init__(self, cfg, input_shape, pretrained=True):
         super().__init__()
-        if cfg.MODEL.DLA.TYPE != "dla34":
-            raise ValueError("only dla34 is built (the BASELINE configuration); got {}".format(cfg.MODEL.DLA.TYPE))
-        base = dla34(pretrained=False, tricks=cfg.MODEL.DLA.TRICKS)
-        self._out_feature_channels = {'p2': 64, 'p3': 128, 'p4': 256, 'p5': 512, 'p6': 512}
+        kind = cfg.MODEL.DLA.TYPE
+        if kind not in DLA_TYPES:
+            raise ValueError("MODEL.DLA.TYPE must be one of {}; got {}".format(", ".join(DLA_TYPES), kind))
+        ctor, channels = DLA_TYPES[kind]
+        # `tricks` only selects a pretrained checkpoint in the reference (dla.py:312-321, 354-388)
+        base = ctor(pretrained=False, tricks=cfg.MODEL.DLA.TRICKS) if kind in ("dla34", "dla60", "dla102") else ctor(pretrained=False)
+        self._out_feature_channels = dict(channels)
         self.base_layer = base.base_layer
         self.level0 = base.level0
         self.level1 = base.level1

@@ -257,6 +257,63 @@ def conv_bwd_data_raw(dy, wt, in_shape, k, stride, pad, accumulate=None):
 
 
 # --------------------------------------------------------------------------
+# grouped 3x3 convolution (DLA's BottleneckX, csrc/conv_grouped.hip): pad 1, Cin == Cout, f32 KRSC weights (Cout, 3, 3, cg) in
+# every precision mode and in all three directions -- no compute copies, no weight bank, no transposed layout
+# --------------------------------------------------------------------------
+def _grouped_out_hw(H, W, stride):
+    return (H - 1) // stride + 1, (W - 1) // stride + 1
+
+
+def conv_grouped_fwd_raw(x, w, groups, stride, bias=None, residual=None, relu=False, stats=None):
+    _need_cuda(x, "conv input")
+    af = _af(x)
+    assert x.is_contiguous() and x.dim() == 4 and w.dtype == f32 and (residual is None or residual.dtype == x.dtype)
+    N, H, W, C = x.shape
+    Ho, Wo = _grouped_out_hw(H, W, stride)
+    assert w.numel() == C * 9 * (C // groups) and (residual is None or tuple(residual.shape) == (N, Ho, Wo, C))
+    assert stats is None or (stats.dtype == f32 and stats.numel() >= (N * Ho * Wo + 63) // 64 * 2 * C)
+    y = torch.empty((N, Ho, Wo, C), dtype=x.dtype, device=x.device)
+    _lib.call("cr_conv2d_grouped_fwd", x, w, y, N, H, W, C, w.shape[0], groups, 3, stride, 1, bias, residual, int(relu), stats, af)
+    return y
+
+
+def conv_grouped_bwd_data_raw(dy, w, in_shape, groups, stride, accumulate=None):
+    """accumulate: as for conv_bwd_data_raw"""
+    N, H, W, C = in_shape
+    assert w.dtype == f32 and dy.is_contiguous() and w.numel() == C * 9 * (C // groups)
+    assert tuple(dy.shape) == (N,) + _grouped_out_hw(H, W, stride) + (C,), "dy does not have the output's shape"
+    dx = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
+    if accumulate is not None:
+        assert tuple(accumulate.shape) == (N, H, W, C), "accumulate must have the input's shape"
+        accumulate = accumulate.to(dy.dtype).contiguous()
+    _lib.call("cr_conv2d_grouped_bwd_data", dy, w, dx, N, H, W, C, dy.shape[3], groups, 3, stride, 1, _af(dy), accumulate)
+    return dx
+
+
+def grouped_wgrad_splits(M):
+    """pixel ranges of cr_conv2d_grouped_bwd_weight (include/cr3dod.h): its workspace holds splits * (C * 9 * cg + C) floats"""
+    rng = max(128, -(-M // 256))
+    return -(-M // rng)
+
+
+def conv_grouped_bwd_weight_raw(dy, x, groups, stride, sink=None, bias_acc=None):
+    """dW (Cout, cg, 3, 3) channels_last, or added into `sink` when given; bias_acc: f32 [Cout] that receives += sum_pixels dy.
+    Never queued (deferred_wgrad): the launch happens here."""
+    N, H, W, C = x.shape
+    assert dy.dtype == x.dtype and dy.is_contiguous() and x.is_contiguous()
+    assert tuple(dy.shape) == (N,) + _grouped_out_hw(H, W, stride) + (C,), "dy does not have the output's shape"
+    cg = C // groups
+    M = dy.shape[0] * dy.shape[1] * dy.shape[2]
+    n_ws = grouped_wgrad_splits(M) * (C * 9 * cg + C)
+    ws = torch.empty((n_ws,), dtype=f32, device=x.device)
+    dw = sink if sink is not None else torch.empty((C, cg, 3, 3), dtype=f32, device=x.device).contiguous(
+        memory_format=torch.channels_last)
+    _lib.call("cr_conv2d_grouped_bwd_weight", dy, x, dw, bias_acc, N, H, W, C, dy.shape[3], groups, 3, stride, 1,
+              int(sink is not None), _af(x), ws, n_ws)
+    return None if sink is not None else dw
+
+
+# --------------------------------------------------------------------------
 # Fan-in of gradients without add kernels.  An activation consumed by several of the ops below would have its gradient
 # contributions summed by autograd with one elementwise add per extra consumer (60 launches per train step).  Instead the
 # consumers of a tensor share a _GradSlot: the FIRST consumer registered in the forward pass must be a convolution -- its
@@ -404,19 +461,24 @@ def conv_bwd_weight_raw(dy, x, k, stride, pad, sink=None, bias_acc=None):
 class _ConvBN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, gamma, beta, residual, running_mean, running_var, stride, pad, relu, eps, momentum,
-                training, slots=((None, 0), (None, 0))):
+                training, slots=((None, 0), (None, 0)), groups=1):
         ctx.slots = slots
+        ctx.groups = groups
         Cout, Cin, k, _ = weight.shape
         dev = x.device
         af = _af(x)
         if training:
-            wb, _ = prepared_weights(weight, x.requires_grad, x.dtype)
+            if groups == 1:
+                wb, _ = prepared_weights(weight, x.requires_grad, x.dtype)
             _STATS_EPOCH[0] += 1
             N_, H_, W_, _ = x.shape
             M = N_ * ((H_ + 2 * pad - k) // stride + 1) * ((W_ + 2 * pad - k) // stride + 1)
             nparts = (M + 63) // 64            # statistics rows are per 64 pixels (independent of the tile choice)
             stats = torch.empty((nparts, 2, Cout), dtype=f32, device=dev)
-            y_raw = conv_fwd_raw(x, wb, Cout, k, stride, pad, stats=stats)
+            if groups == 1:
+                y_raw = conv_fwd_raw(x, wb, Cout, k, stride, pad, stats=stats)
+            else:
+                y_raw = conv_grouped_fwd_raw(x, weight.detach(), groups, stride, stats=stats)
             out = torch.empty_like(y_raw)
             mi = torch.empty((2, Cout), dtype=f32, device=dev)
             _lib.call("cr_bn_fwd", y_raw, stats, nparts, gamma.detach(), beta.detach(), residual, out, M, Cout, int(relu),
@@ -432,12 +494,15 @@ class _ConvBN(torch.autograd.Function):
             bias_f = torch.empty((Cout,), dtype=f32, device=dev)
             _lib.call("cr_fold_bn", weight.detach(), gamma.detach(), beta.detach(), running_mean, running_var, float(eps), wf32,
                       bias_f, Cout, K_, 1)
-            if x.dtype == bf16:
-                wf = torch.empty((Cout, K_), dtype=bf16, device=dev)
-                _lib.call("cr_cast_f32_to_bf16", wf32, wf, wf32.numel())
+            if groups > 1:                  # the grouped kernels read f32 weights in every mode
+                out = conv_grouped_fwd_raw(x, wf32, groups, stride, bias=bias_f, residual=residual, relu=relu)
             else:
-                wf = wf32
-            out = conv_fwd_raw(x, wf, Cout, k, stride, pad, bias=bias_f, residual=residual, relu=relu)
+                if x.dtype == bf16:
+                    wf = torch.empty((Cout, K_), dtype=bf16, device=dev)
+                    _lib.call("cr_cast_f32_to_bf16", wf32, wf, wf32.numel())
+                else:
+                    wf = wf32
+                out = conv_fwd_raw(x, wf, Cout, k, stride, pad, bias=bias_f, residual=residual, relu=relu)
             y_raw, mi = wf32, None
             ctx.frozen = (running_mean, running_var, float(eps))
         ctx.cfg = (k, stride, pad, relu, training, residual is not None)
@@ -487,19 +552,28 @@ class _ConvBN(torch.autograd.Function):
             _slot_put(rslot, dres)
             dres = None
         dx = None
+        groups = ctx.groups
         if need_dx:
-            _, wt = prepared_weights(weight, True, x.dtype)
-            if xslot is not None and xi > 1:                # not the first consumer of x: leave the contribution in the slot
-                _slot_put(xslot, conv_bwd_data_raw(dx_raw, wt, x.shape, k, stride, pad, accumulate=_slot_fold(xslot)))
+            if groups == 1:
+                _, wt = prepared_weights(weight, True, x.dtype)
+                bwd_data = lambda acc: conv_bwd_data_raw(dx_raw, wt, x.shape, k, stride, pad, accumulate=acc)
             else:
-                acc = _slot_take(xslot) if xslot is not None else None
-                dx = conv_bwd_data_raw(dx_raw, wt, x.shape, k, stride, pad, accumulate=acc)
+                bwd_data = lambda acc: conv_grouped_bwd_data_raw(dx_raw, weight.detach(), x.shape, groups, stride, accumulate=acc)
+            if xslot is not None and xi > 1:                # not the first consumer of x: leave the contribution in the slot
+                _slot_put(xslot, bwd_data(_slot_fold(xslot)))
+            else:
+                dx = bwd_data(_slot_take(xslot) if xslot is not None else None)
         elif xslot is not None:
             raise RuntimeError("gradient slot registered for an input that needs no gradient")
-        dw = conv_bwd_weight_raw(dx_raw, x, k, stride, pad, grad_sink(weight)) if need_dw else None
+        if not need_dw:
+            dw = None
+        elif groups == 1:
+            dw = conv_bwd_weight_raw(dx_raw, x, k, stride, pad, grad_sink(weight))
+        else:
+            dw = conv_grouped_bwd_weight_raw(dx_raw, x, groups, stride, grad_sink(weight))
         if root:
             return dx_raw, dw, ret_g, ret_b
-        return dx, dw, ret_g, ret_b, dres, None, None, None, None, None, None, None, None, None
+        return dx, dw, ret_g, ret_b, dres, None, None, None, None, None, None, None, None, None, None
 
     @staticmethod
     def _frozen_backward(ctx, dout, need_dx, need_dw, root):
@@ -521,22 +595,30 @@ class _ConvBN(torch.autograd.Function):
             _slot_put(rslot, dres)
             dres = None
         dx = None
+        groups = ctx.groups
         if need_dx or root:
-            wt = torch.empty((Cin, k * k * Cout), dtype=x.dtype, device=dev)        # [Cin][k*k][Cout]
-            assert wt.numel() == wf32.numel()
-            _lib.call("cr_weight_transpose", wf32, wt, Cout, k, Cin, int(x.dtype == f32))
+            if groups == 1:
+                wt = torch.empty((Cin, k * k * Cout), dtype=x.dtype, device=dev)        # [Cin][k*k][Cout]
+                assert wt.numel() == wf32.numel()
+                _lib.call("cr_weight_transpose", wf32, wt, Cout, k, Cin, int(x.dtype == f32))
+                bwd_data = lambda acc: conv_bwd_data_raw(g, wt, x.shape, k, stride, pad, accumulate=acc)
+            else:                                           # the grouped backward-data reads the folded f32 weights as they are
+                wt = None
+                bwd_data = lambda acc: conv_grouped_bwd_data_raw(g, wf32, x.shape, groups, stride, accumulate=acc)
             if root:
                 ctx.frozen_wt = wt
             elif xslot is not None and xi > 1:              # not the first consumer of x: leave the contribution in the slot
-                _slot_put(xslot, conv_bwd_data_raw(g, wt, x.shape, k, stride, pad, accumulate=_slot_fold(xslot)))
+                _slot_put(xslot, bwd_data(_slot_fold(xslot)))
             else:
-                acc = _slot_take(xslot) if xslot is not None else None
-                dx = conv_bwd_data_raw(g, wt, x.shape, k, stride, pad, accumulate=acc)
+                dx = bwd_data(_slot_take(xslot) if xslot is not None else None)
         elif xslot is not None:
             raise RuntimeError("gradient slot registered for an input that needs no gradient")
         # dgamma needs <dwf, w> even when the weight itself needs no gradient; sum_p g rides on the weight-gradient launch
         sg = torch.zeros((Cout,), dtype=f32, device=dev)
-        dwf = conv_bwd_weight_raw(g, x, k, stride, pad, None, bias_acc=sg)
+        if groups == 1:
+            dwf = conv_bwd_weight_raw(g, x, k, stride, pad, None, bias_acc=sg)
+        else:
+            dwf = conv_grouped_bwd_weight_raw(g, x, groups, stride, None, bias_acc=sg)
         wsink = grad_sink(weight) if need_dw else None
         dw = None
         if need_dw and wsink is None:
@@ -554,7 +636,7 @@ class _ConvBN(torch.autograd.Function):
                   int(wsink is not None), dgamma, dbeta, Cout, K_)
         if root:
             return g, dw, ret_g, ret_b
-        return dx, dw, ret_g, ret_b, dres, None, None, None, None, None, None, None, None, None
+        return dx, dw, ret_g, ret_b, dres, None, None, None, None, None, None, None, None, None, None
 
 
 class _RootConvBN(torch.autograd.Function):
@@ -635,7 +717,8 @@ def refresh_folds(reg):
         e["tag"] = tag
 
 
-def conv_bn_folded(x, weight, gamma, beta, running_mean, running_var, stride=1, pad=0, relu=True, residual=None, eps=1e-5):
+def conv_bn_folded(x, weight, gamma, beta, running_mean, running_var, stride=1, pad=0, relu=True, residual=None, eps=1e-5,
+                   groups=1):
     """inference: frozen BatchNorm folded into the convolution's weights and bias (cr_fold_bn), residual and ReLU in the
     conv epilogue -- one kernel per layer instead of conv + scale/shift arithmetic + a second pass over the output.
     Outside graph capture the folded copies are cached on the weight tensor (keyed by the version counters of the five
@@ -647,6 +730,14 @@ def conv_bn_folded(x, weight, gamma, beta, running_mean, running_var, stride=1, 
     K_ = weight.numel() // Cout
     capturing = torch.cuda.is_current_stream_capturing()
     attr = "_cr_fold" if x.dtype == bf16 else "_cr_fold32"
+    if groups == 1:
+        fold_af, fold_dtype = _af(x), x.dtype
+        fwd = lambda wf, bias_f: conv_fwd_raw(x, wf, Cout, k, stride, pad, bias=bias_f, residual=residual, relu=relu)
+    else:                       # grouped 3x3: the folded weights stay f32 in every mode (cr_conv2d_grouped_fwd reads f32)
+        if k != 3 or pad != 1:
+            raise _lib.CrError(f"grouped convolution: only 3x3 with padding 1 (got k {k}, pad {pad})")
+        fold_af, fold_dtype = 1, f32
+        fwd = lambda wf, bias_f: conv_grouped_fwd_raw(x, wf, groups, stride, bias=bias_f, residual=residual, relu=relu)
     warm = getattr(weight, attr, None)
     if capturing and _FOLD_REG[0] is not None and warm is not None:
         # eval-mode graph with externally refreshed folds: the graph only READS the folded copies; refresh_folds() rewrites
@@ -655,38 +746,41 @@ def conv_bn_folded(x, weight, gamma, beta, running_mean, running_var, stride=1, 
         # its block with an earlier intermediate of the graph, which every replay rewrites.
         _, wf, bias_f = warm
         _FOLD_REG[0].append({"t": (weight, gamma, beta, running_mean, running_var), "eps": float(eps), "wf": wf, "b": bias_f,
-                             "tag": None, "af": _af(x), "K": K_, "Cout": Cout})
+                             "tag": None, "af": fold_af, "K": K_, "Cout": Cout})
         try:
             delattr(weight, attr)           # the graph owns these buffers now: eager calls make their own
         except Exception:
             pass
-        return conv_fwd_raw(x, wf, Cout, k, stride, pad, bias=bias_f, residual=residual, relu=relu)
+        return fwd(wf, bias_f)
     tag = None if capturing else (weight._version, gamma._version, beta._version, running_mean._version, running_var._version,
                                   _WEIGHT_EPOCH[0], _STATS_EPOCH[0], weight.data_ptr(), running_mean.data_ptr(), float(eps))
     ent = None if capturing else warm
     if ent is None or ent[0] != tag:
-        wf = torch.empty((Cout, K_), dtype=x.dtype, device=x.device)
+        wf = torch.empty((Cout, K_), dtype=fold_dtype, device=x.device)
         bias_f = torch.empty((Cout,), dtype=f32, device=x.device)
         _lib.call("cr_fold_bn", weight.detach(), gamma.detach(), beta.detach(), running_mean, running_var, float(eps), wf, bias_f,
-                  Cout, K_, _af(x))
+                  Cout, K_, fold_af)
         ent = (tag, wf, bias_f)
         if not capturing:
             try:
                 setattr(weight, attr, ent)
             except Exception:
                 pass
-    return conv_fwd_raw(x, ent[1], Cout, k, stride, pad, bias=ent[2], residual=residual, relu=relu)
+    return fwd(ent[1], ent[2])
 
 
 def conv_bn_act(x, weight, gamma, beta, running_mean, running_var, stride=1, pad=0, relu=True, residual=None,
-                eps=1e-5, momentum=0.1, training=True):
+                eps=1e-5, momentum=0.1, training=True, groups=1):
+    """groups > 1: the grouped 3x3 kernels (cr_conv2d_grouped_*; pad 1, Cin == Cout) in every route below"""
     if not training and not (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or gamma.requires_grad
                                                           or (residual is not None and residual.requires_grad))):
-        return conv_bn_folded(x, weight, gamma, beta, running_mean, running_var, stride, pad, relu, residual, eps)
+        return conv_bn_folded(x, weight, gamma, beta, running_mean, running_var, stride, pad, relu, residual, eps, groups)
+    if groups > 1 and (weight.shape[2] != 3 or pad != 1):
+        raise _lib.CrError(f"grouped convolution: only 3x3 with padding 1 (got k {weight.shape[2]}, pad {pad})")
     xs = _slot_register(x, True)
     rs = _slot_register(residual, False) if residual is not None else (None, 0)
     return _ConvBN.apply(x, as_krsc(weight), gamma, beta, residual, running_mean, running_var, stride, pad, relu, eps,
-                         momentum, training, (xs, rs))
+                         momentum, training, (xs, rs), groups)
 
 
 # --------------------------------------------------------------------------

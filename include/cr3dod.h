@@ -300,6 +300,28 @@ int cr_fold_bn(cr_ctx* ctx, const float* w, const float* gamma, const float* bet
  * the same kernel from the dy tiles it stages anyway (dbias must be zeroed or hold the running gradient). */
 int cr_conv2d_bwd_weight_bias(cr_ctx* ctx, const void* dy, const void* x, float* dw, float* dbias, int N, int H, int W,
                               int Cin, int Cout, int ks, int stride, int pad, int accumulate, int act_f32);
+/* Grouped 3x3 convolution (csrc/conv_grouped.hip): nn.Conv2d(C, C, 3, stride, padding=1, groups=cardinality) of DLA's
+ * BottleneckX (cubercnn/modeling/backbone/dla.py:112-153; cardinality 32, 64 for dla102x2 at dla.py:400-406).  Direct
+ * convolution on the vector ALU, f32 accumulation.  ks = 3, pad = 1, stride in {1,2}, Cin == Cout, groups in {32,64},
+ * cg = Cin / groups in {2,4,8,16,32}, any N, H, W >= 1; anything else returns CR_EINVAL without a launch.
+ * x / y / dy / dx / residual / accumulate NHWC bf16 or f32 (act_f32 != 0; 1 and 2 run the same f32 arithmetic);
+ * w f32 (Cout, 3, 3, cg) = the channels_last storage of the (Cout, cg, 3, 3) parameter, in all three directions.
+ *   fwd         y = relu?(conv(x, w) + bias? + residual?); stats: optional f32 [ceil(M/64)][2][Cout], M = N*Ho*Wo, per 64
+ *               output pixels the per-channel sum / sum of squares of the stored conv output before residual and ReLU --
+ *               the layout cr_bn_fwd reads (every entry written, fixed order, no atomics).
+ *   bwd_data    dx = conv^T(dy, w) + accumulate? (accumulate as for cr_conv2d_bwd_data).
+ *   bwd_weight  dw = (accumulate ? dw : 0) + sum_p dy x; dbias (may be NULL) += sum_p dy.  No atomics: pixel range s of
+ *               splits = ceil(M / max(128, ceil(M/256))) writes its partial sums into ws, which must hold
+ *               splits * (Cout*9*cg + Cout) floats (ws_floats), and a second pass adds the ranges in index order:
+ *               bit-identical from run to run. */
+int cr_conv2d_grouped_fwd(cr_ctx* ctx, const void* x, const float* w, void* y, int N, int H, int W, int Cin, int Cout,
+                          int groups, int ks, int stride, int pad, const float* bias, const void* residual, int relu,
+                          float* stats, int act_f32);
+int cr_conv2d_grouped_bwd_data(cr_ctx* ctx, const void* dy, const float* w, void* dx, int N, int H, int W, int Cin,
+                               int Cout, int groups, int ks, int stride, int pad, int act_f32, const void* accumulate);
+int cr_conv2d_grouped_bwd_weight(cr_ctx* ctx, const void* dy, const void* x, float* dw, float* dbias, int N, int H, int W,
+                                 int Cin, int Cout, int groups, int ks, int stride, int pad, int accumulate, int act_f32,
+                                 float* ws, int64_t ws_floats);
 /* Winograd F(2x2, 3x3) transforms for stride-1, pad-1 3x3 convolutions on float32 NHWC maps (csrc/winograd.hip): the 16
  * products over channels in between are 1x1 grouped convolutions (cr_conv2d_fwd_group) on V / U / M -- the arithmetic replaces
  * torch.nn.functional.conv2d as called by detectron2's RPN head / FPN output convolutions in the reference's model.

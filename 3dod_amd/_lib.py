@@ -84,6 +84,9 @@ SIGNATURES = {
     "cr_conv2d_bwd_weight_group": [P, c_int, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int],
     "cr_conv2d_bwd_weight_multi": [P, c_int, P, P, P, P, P, P, P, P, P, P, P, P, c_int],
     "cr_roi_align_bwd_set": [P, P, P, P, P, c_int, c_int, c_int, P, c_int64, c_int, c_int, P, c_int],
+    "cr_roi_pool_fwd": [P, P, P, P, P, c_int, c_int, c_int, P, c_int64, c_int, c_int, c_int, c_int, P, P, c_int],
+    "cr_roi_pool_bwd": [P, P, P, P, P, c_int, c_int, c_int, P, c_int64, c_int, c_int, c_int, c_int, P, P, c_int],
+    "cr_roi_pool_bwd_set": [P, P, P, P, P, c_int, c_int, c_int, P, c_int64, c_int, c_int, c_int, c_int, P, c_int],
     "cr_nms_grouped": [P, P, P, c_int, c_int, c_float, P, P],
     "cr_cube_loss_fwd": [P, P, c_int64, c_int, c_int, c_int, c_int, P, P],
     "cr_cube_loss_bwd": [P, P, c_int64, c_int, c_int, c_int, c_int, P, P, P, P, P, P],

@@ -1,11 +1,14 @@
-// Detection-side kernels: ROIAlign (aligned, adaptive sampling) forward/backward over the FPN
-// pyramid with the level assignment fused in, grouped NMS, and RPN anchor decoding.
+// Detection-side kernels: the RoI pooler (ROIAlignV2 = aligned, adaptive sampling: the default; ROIAlign, a fixed
+// sampling ratio and ROIPool behind cr_roi_pool_*) forward/backward over the FPN pyramid with the level assignment
+// fused in, grouped NMS, and RPN anchor decoding.
 //
 // Reference call sites (paths into the reference tree); the arithmetic itself lives in
 // third-party code that is absent from the reference and is restated from its published
 // definition (parity unpinned, pinned here by a torch restatement in oracle/):
 //   ROIPooler(ROIAlignV2 7x7, sampling_ratio 0)  cubercnn/modeling/roi_heads/roi_heads.py:2075-2080,2178,2273
 //        = torchvision roi_align(aligned=True) + detectron2 assign_boxes_to_levels
+//   ROIPooler(POOLER_TYPE ROIAlign | ROIPool, POOLER_SAMPLING_RATIO s)   cubercnn/config/config.py:43-45, roi_heads.py:2071-2080
+//        = torchvision roi_align(aligned=False) / roi_pool, sampling_ratio=s
 //   nms / batched_nms                              cubercnn/modeling/roi_heads/fast_rcnn.py:105; detectron2 RPN
 #include "cr_common.h"
 #include <math.h>
@@ -19,6 +22,7 @@ struct Pyramid {
     int H[MAX_LEVELS], W[MAX_LEVELS];
     float scale[MAX_LEVELS];
     int nlev, C, min_level;        // min_level = log2(stride of level 0)
+    int ptype, sratio, nimg;       // sample geometry + batch size of the GEO = 1 kernels (RoiAxis below); the GEO = 0 ones never read them
 };
 
 // detectron2 assign_boxes_to_levels: floor(4 + log2(sqrt(area)/224 + 1e-8)) clamped to the pyramid
@@ -28,6 +32,34 @@ __device__ __forceinline__ int roi_level(const float* b, const Pyramid& py) {
     const float lo = (float)py.min_level, hi = (float)(py.min_level + py.nlev - 1);
     lv = fminf(fmaxf(lv, lo), hi);
     return (int)lv - py.min_level;
+}
+
+// Sample geometry of one axis of a RoI on its level's map: sample i of bin p sits at start + p * bin + (i + 0.5) * bin / grid.
+//   GEO 0  ROIAlignV2, adaptive grid: compile-time constants, the code the default configuration has always run.
+//   GEO 1  py.ptype 0 ROIAlignV2 (half-pixel offset, extent not clamped) | 1 ROIAlign (no offset, extent >= 1 px);
+//          py.sratio > 0: that many samples per bin and axis, 0: ceil(extent / P).
+//   GEO 2  the geometry of GEO 0 (same constants, same bits) behind cr_roi_pool_*.
+// GEO 1 and 2 also drop RoIs whose image index is outside [0, py.nimg): the entry points of GEO 0 leave that to their caller
+// (only their tile-owner backward checks it).
+// (The comparison, not fmaxf, clamps the extent: a NaN extent stays NaN, so a non-finite RoI still samples nothing.)
+struct RoiAxis { float start, bin; int grid; };
+template <int GEO>
+__device__ __forceinline__ RoiAxis roi_axis(const Pyramid& py, float a1, float a2, float sc, int P) {
+    RoiAxis g;
+    if (GEO != 1) {
+        g.start = a1 * sc - 0.5f;
+        const float len = (a2 - a1) * sc;                 // aligned: no 1-px floor
+        g.bin = len / (float)P;
+        g.grid = (int)ceilf(len / (float)P);
+    } else {
+        const bool v2 = py.ptype == 0;
+        g.start = v2 ? a1 * sc - 0.5f : a1 * sc;
+        float len = (a2 - a1) * sc;
+        if (!v2 && len < 1.0f) len = 1.0f;
+        g.bin = len / (float)P;
+        g.grid = py.sratio > 0 ? py.sratio : (int)ceilf(len / (float)P);
+    }
+    return g;
 }
 
 struct Samp { int yl, yh, xl, xh; float w1, w2, w3, w4; bool ok; };
@@ -46,7 +78,7 @@ __device__ __forceinline__ Samp bilinear(float y, float x, int H, int W) {
 }
 
 // one thread = (roi, ph, pw, 8 channels).  rois (R,5) = [batch, x1,y1,x2,y2].  out (R,PH,PW,C) in the storage type T
-template <bool BWD, typename T>
+template <bool BWD, typename T, int GEO = 0>
 __global__ __launch_bounds__(256) void k_roi_align(Pyramid py, const float* __restrict__ rois, int R, int PH, int PW,
                                                    T* __restrict__ out, const T* __restrict__ dout) {
     const int cg = py.C >> 3;
@@ -62,10 +94,10 @@ __global__ __launch_bounds__(256) void k_roi_align(Pyramid py, const float* __re
     const int lv = roi_level(rb + 1, py);
     const int H = py.H[lv], W = py.W[lv];
     const float sc = py.scale[lv];
-    const float x1 = rb[1] * sc - 0.5f, y1 = rb[2] * sc - 0.5f;
-    const float rw = (rb[3] - rb[1]) * sc, rh = (rb[4] - rb[2]) * sc;     // aligned: no 1-px floor
-    const float bw = rw / (float)PW, bh = rh / (float)PH;
-    const int gh = (int)ceilf(rh / (float)PH), gw = (int)ceilf(rw / (float)PW);
+    const RoiAxis gx = roi_axis<GEO>(py, rb[1], rb[3], sc, PW), gy = roi_axis<GEO>(py, rb[2], rb[4], sc, PH);
+    const float x1 = gx.start, y1 = gy.start, bw = gx.bin, bh = gy.bin;
+    int gh = gy.grid, gw = gx.grid;
+    if (GEO != 0 && (n < 0 || n >= py.nimg)) gh = gw = 0;     // image index outside the batch: zeros, no gradient
     const float cnt = fmaxf((float)(gh * gw), 1.f);
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     float g8[8];
@@ -110,7 +142,7 @@ __global__ __launch_bounds__(256) void k_roi_align(Pyramid py, const float* __re
 
 // backward: one thread = (roi, ph, pw, ONE channel), channel fastest, so every atomic wave-instruction adds
 // 64 consecutive floats (256 contiguous bytes: the full-rate shape of MI355X_MICROARCH.md "Global float atomics").
-template <typename T>
+template <typename T, int GEO = 0>
 __global__ __launch_bounds__(256) void k_roi_align_bwd(Pyramid py, const float* __restrict__ rois, int R, int PH,
                                                        int PW, const T* __restrict__ dout) {
     const int C = py.C;
@@ -126,12 +158,12 @@ __global__ __launch_bounds__(256) void k_roi_align_bwd(Pyramid py, const float* 
     const int lv = roi_level(rb + 1, py);
     const int H = py.H[lv], W = py.W[lv];
     const float sc = py.scale[lv];
-    const float x1 = rb[1] * sc - 0.5f, y1 = rb[2] * sc - 0.5f;
-    const float rw = (rb[3] - rb[1]) * sc, rh = (rb[4] - rb[2]) * sc;
-    const float bw = rw / (float)PW, bh = rh / (float)PH;
-    const int gh = (int)ceilf(rh / (float)PH), gw = (int)ceilf(rw / (float)PW);
+    const RoiAxis gx = roi_axis<GEO>(py, rb[1], rb[3], sc, PW), gy = roi_axis<GEO>(py, rb[2], rb[4], sc, PH);
+    const float x1 = gx.start, y1 = gy.start, bw = gx.bin, bh = gy.bin;
+    const int gh = gy.grid, gw = gx.grid;
     const float cnt = fmaxf((float)(gh * gw), 1.f);
     const float g = load1<T>(dout, (size_t)i) / cnt;
+    if (GEO != 0 && (n < 0 || n >= py.nimg)) return;
     if (g == 0.f) return;        // masked-out (padding) RoIs and dead channels add nothing: skip their 16 atomics
     float* gq = py.grad[lv] + (size_t)n * H * W * C + c;
     for (int iy = 0; iy < gh; ++iy) {
@@ -172,7 +204,7 @@ __device__ __forceinline__ Lin1 lin1(float y, int H) {
 // is only ever added to from ONE XCD: the atomics stay in that XCD's L2 instead of the line migrating between the L2s of
 // all the XCDs whose RoIs overlap there.  (Performance only: the L2s are coherent, any other dispatch order gives the same
 // sums.)  The block's threads split the footprint rows: thread = (row phase t / CB, channel t % CB).
-template <int P, typename T, int XG>
+template <int P, typename T, int XG, int GEO = 0>
 __global__ __launch_bounds__(256) void k_roi_align_bwd_sep(Pyramid py, const float* __restrict__ rois, int R,
                                                            const T* __restrict__ dout, int maxH) {
     extern __shared__ float sm[];                        // Ay [maxH][P] | Ax [maxW][P]
@@ -187,10 +219,9 @@ __global__ __launch_bounds__(256) void k_roi_align_bwd_sep(Pyramid py, const flo
     const int lv = roi_level(rb + 1, py);
     const int H = py.H[lv], W = py.W[lv];
     const float sc = py.scale[lv];
-    const float x1 = rb[1] * sc - 0.5f, y1 = rb[2] * sc - 0.5f;
-    const float rw = (rb[3] - rb[1]) * sc, rh = (rb[4] - rb[2]) * sc;
-    const float bw = rw / (float)P, bh = rh / (float)P;
-    const int gh = min((int)ceilf(rh / (float)P), 4096), gw = min((int)ceilf(rw / (float)P), 4096);
+    const RoiAxis gx = roi_axis<GEO>(py, rb[1], rb[3], sc, P), gy = roi_axis<GEO>(py, rb[2], rb[4], sc, P);
+    const float x1 = gx.start, y1 = gy.start, bw = gx.bin, bh = gy.bin;
+    const int gh = min(gy.grid, 4096), gw = min(gx.grid, 4096);
     if (t < 2) { s_lo[t] = 0x7fffffff; s_hi[t] = -1; }
     __syncthreads();
     // pass 1: footprint extent per axis (threads 0..P-1 rows, P..2P-1 columns)
@@ -209,6 +240,7 @@ __global__ __launch_bounds__(256) void k_roi_align_bwd_sep(Pyramid py, const flo
     __syncthreads();
     const int y0 = s_lo[0], Py = s_hi[0] - y0 + 1, x0 = s_lo[1], Px = s_hi[1] - x0 + 1;
     if (s_hi[0] < 0 || s_hi[1] < 0 || n < 0) return;     // no valid sample at all (block-uniform)
+    if (GEO != 0 && n >= py.nimg) return;
     for (int i = t; i < Py * P; i += (int)blockDim.x) Ay[i] = 0.f;
     for (int i = t; i < Px * P; i += (int)blockDim.x) Ax[i] = 0.f;
     __syncthreads();
@@ -277,7 +309,7 @@ __global__ __launch_bounds__(256) void k_roi_align_bwd_sep(Pyramid py, const flo
 #define RT_BATCH 16
 struct RoiExt { int lv, n, y0, y1, x0, x1, pad0, pad1; };      // footprint rows y0..y1 / columns x0..x1 (y1 < y0: none)
 
-template <int P>
+template <int P, int GEO = 0>
 __global__ __launch_bounds__(256) void k_roi_bbox(Pyramid py, const float* __restrict__ rois, int R, int N,
                                                   RoiExt* __restrict__ ext) {
     const int r = blockIdx.x * 256 + threadIdx.x;
@@ -289,10 +321,9 @@ __global__ __launch_bounds__(256) void k_roi_bbox(Pyramid py, const float* __res
     e.pad0 = e.pad1 = 0;
     const int H = py.H[e.lv], W = py.W[e.lv];
     const float sc = py.scale[e.lv];
-    const float x1 = rb[1] * sc - 0.5f, y1 = rb[2] * sc - 0.5f;
-    const float rw = (rb[3] - rb[1]) * sc, rh = (rb[4] - rb[2]) * sc;
-    const float bw = rw / (float)P, bh = rh / (float)P;
-    const int gh = min((int)ceilf(rh / (float)P), 4096), gw = min((int)ceilf(rw / (float)P), 4096);
+    const RoiAxis gx = roi_axis<GEO>(py, rb[1], rb[3], sc, P), gy = roi_axis<GEO>(py, rb[2], rb[4], sc, P);
+    const float x1 = gx.start, y1 = gy.start, bw = gx.bin, bh = gy.bin;
+    const int gh = min(gy.grid, 4096), gw = min(gx.grid, 4096);
     int lo[2] = {0x7fffffff, 0x7fffffff}, hi[2] = {-1, -1};
 #pragma unroll
     for (int ax = 0; ax < 2; ++ax) {
@@ -371,7 +402,7 @@ template <typename T, int A, int P> __device__ __forceinline__ void rt_read_row(
     }
 }
 
-template <int P, typename T>
+template <int P, typename T, int GEO = 0>
 __global__ __launch_bounds__(256, 2) void k_roi_bwd_tiles(Pyramid py, TileMap tm, const float* __restrict__ rois, int R,
                                                           const T* __restrict__ dout, const RoiExt* __restrict__ ext) {
     static_assert(P == 7, "built for 7 x 7 pooling");
@@ -431,10 +462,9 @@ __global__ __launch_bounds__(256, 2) void k_roi_bwd_tiles(Pyramid py, TileMap tm
                 // thread (RoI j of the batch, axis, bin p): column p of Ay / Ax restricted to the tile's 16 rows / columns
                 const int j = u / (2 * P), ax = (u / P) & 1, p = u % P;
                 const float* rb = rois + (size_t)s_queue[q0 + j] * 5;
-                const float o1 = (ax ? rb[1] : rb[2]) * sc - 0.5f;
-                const float len = ((ax ? rb[3] : rb[4]) - (ax ? rb[1] : rb[2])) * sc;
-                const float bsz = len / (float)P;
-                const int gN = min((int)ceilf(len / (float)P), 4096), L = ax ? W : H, base = ax ? tx0 : ty0;
+                const RoiAxis ga = roi_axis<GEO>(py, ax ? rb[1] : rb[2], ax ? rb[3] : rb[4], sc, P);
+                const float o1 = ga.start, bsz = ga.bin;
+                const int gN = min(ga.grid, 4096), L = ax ? W : H, base = ax ? tx0 : ty0;
                 float* A = s_A[j][ax][p];
 #pragma unroll
                 for (int i = 0; i < RT_TILE; i += 4) *reinterpret_cast<float4*>(A + i) = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -573,6 +603,96 @@ __global__ __launch_bounds__(256, 2) void k_roi_bwd_tiles(Pyramid py, TileMap tm
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// ROIPool (torchvision roi_pool, restated): quantised RoI, bin p covers [floor(p * bin), ceil((p + 1) * bin)) shifted by the
+// RoI's start and clipped to the map; output = the bin's maximum scanned row-major from -FLT_MAX with a strict > (the first
+// maximum wins, a NaN never wins), an empty bin gives 0.  The bin bounds are float32 with one rounding per operation
+// (correctly rounded division, nothing contracted across floor / ceil).
+// ---------------------------------------------------------------------------------------------------------------
+struct PoolBin { int y0, y1, x0, x1; bool ok; };
+__device__ __forceinline__ PoolBin pool_bin(const float* rb, int n, int nimg, float sc, int H, int W, int ph, int pw, int PH,
+                                            int PW) {
+#pragma clang fp contract(off)
+    PoolBin b;
+    b.ok = n >= 0 && n < nimg && isfinite(rb[1]) && isfinite(rb[2]) && isfinite(rb[3]) && isfinite(rb[4]);
+    b.y0 = b.y1 = b.x0 = b.x1 = 0;
+    if (!b.ok) return b;
+    // (a finite product beyond the int range saturates in the conversion; such a RoI covers nothing or everything)
+    const float fsw = fminf(fmaxf(roundf(rb[1] * sc), -1.0e9f), 1.0e9f), fsh = fminf(fmaxf(roundf(rb[2] * sc), -1.0e9f), 1.0e9f);
+    const float few = fminf(fmaxf(roundf(rb[3] * sc), -1.0e9f), 1.0e9f), feh = fminf(fmaxf(roundf(rb[4] * sc), -1.0e9f), 1.0e9f);
+    const int sw = (int)fsw, sh = (int)fsh, ew = (int)few, eh = (int)feh;
+    const int rw = max(ew - sw + 1, 1), rh = max(eh - sh + 1, 1);
+    const float bh = (float)rh / (float)PH, bw = (float)rw / (float)PW;
+    const int hs = (int)floorf((float)ph * bh), he = (int)ceilf((float)(ph + 1) * bh);
+    const int ws = (int)floorf((float)pw * bw), we = (int)ceilf((float)(pw + 1) * bw);
+    b.y0 = min(max(hs + sh, 0), H); b.y1 = min(max(he + sh, 0), H);
+    b.x0 = min(max(ws + sw, 0), W); b.x1 = min(max(we + sw, 0), W);
+    return b;
+}
+
+// one thread = (roi, ph, pw, 8 channels), like k_roi_align.  argmax (R,PH,PW,C) int32: y * W + x on the RoI's level, -1 where
+// nothing won (empty bin, dropped RoI)
+template <typename T>
+__global__ __launch_bounds__(256) void k_roi_pool_fwd(Pyramid py, const float* __restrict__ rois, int R, int PH, int PW,
+                                                      T* __restrict__ out, int* __restrict__ argmax) {
+    const int cg = py.C >> 3;
+    const int64_t total = (int64_t)R * PH * PW * cg;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)(i % cg);
+    const int pw = (int)((i / cg) % PW);
+    const int ph = (int)((i / ((int64_t)cg * PW)) % PH);
+    const int r = (int)(i / ((int64_t)cg * PW * PH));
+    const float* rb = rois + (size_t)r * 5;
+    const int n = (int)rb[0];
+    const int lv = roi_level(rb + 1, py);
+    const int H = py.H[lv], W = py.W[lv];
+    const PoolBin b = pool_bin(rb, n, py.nimg, py.scale[lv], H, W, ph, pw, PH, PW);
+    const bool empty = !b.ok || b.y1 <= b.y0 || b.x1 <= b.x0;
+    float best[8];
+    int arg[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { best[e] = empty ? 0.f : -3.402823466e+38f; arg[e] = -1; }
+    if (!empty) {
+        const T* f = (const T*)py.feat[lv] + (size_t)n * H * W * py.C + c * 8;
+        for (int y = b.y0; y < b.y1; ++y)
+            for (int x = b.x0; x < b.x1; ++x) {
+                float v[8];
+                load8<T>(f, ((size_t)y * W + x) * py.C, v);
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (v[e] > best[e]) { best[e] = v[e]; arg[e] = y * W + x; }
+            }
+    }
+    store8<T>(out, (size_t)i * 8, best);
+    int4* a4 = reinterpret_cast<int4*>(argmax + (size_t)i * 8);
+    a4[0] = make_int4(arg[0], arg[1], arg[2], arg[3]);
+    a4[1] = make_int4(arg[4], arg[5], arg[6], arg[7]);
+}
+
+// backward: one thread = (roi, ph, pw, ONE channel), channel fastest: 64 consecutive floats per atomic wave-instruction,
+// like k_roi_align_bwd.  Adds dY to the argmax pixel; a zero gradient or an argmax of -1 adds nothing.
+template <typename T>
+__global__ __launch_bounds__(256) void k_roi_pool_bwd(Pyramid py, const float* __restrict__ rois, int R, int PH, int PW,
+                                                      const T* __restrict__ dout, const int* __restrict__ argmax) {
+    const int C = py.C;
+    const int64_t total = (int64_t)R * PH * PW * C;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int a = argmax[i];
+    const float g = load1<T>(dout, (size_t)i);
+    if (a < 0 || g == 0.f) return;
+    const int c = (int)(i % C);
+    const int r = (int)(i / ((int64_t)C * PW * PH));
+    const float* rb = rois + (size_t)r * 5;
+    const int n = (int)rb[0];
+    const int lv = roi_level(rb + 1, py);
+    const int H = py.H[lv], W = py.W[lv];
+    if (n < 0 || n >= py.nimg || a >= H * W) return;     // (an argmax the forward of these RoIs cannot have written)
+    atomicAdd(py.grad[lv] + ((size_t)n * H * W + a) * C + c, g);
+}
+
 static int fill_pyramid(Pyramid& py, const void* const* feats, float* const* grads, const int* Hs, const int* Ws,
                         const float* scales, int nlev, int C) {
     CR_CHECK_ARG(nlev >= 1 && nlev <= MAX_LEVELS, "roi_align: 1..%d levels", MAX_LEVELS);
@@ -584,6 +704,90 @@ static int fill_pyramid(Pyramid& py, const void* const* feats, float* const* gra
         py.H[l] = Hs[l]; py.W[l] = Ws[l]; py.scale[l] = scales[l];
     }
     py.min_level = (int)lroundf(-log2f(scales[0]));
+    py.ptype = 0; py.sratio = 0; py.nimg = 0;
+    return CR_OK;
+}
+
+// The launches behind the entry points, per sample geometry (GEO 0: the default configuration's kernels).
+template <int GEO>
+static int launch_roi_fwd(cr_ctx* ctx, const Pyramid& py, const float* rois, int64_t R, int PH, int PW, void* out, int act_f32) {
+    const int64_t total = R * PH * PW * (py.C / 8);
+    if (act_f32)
+        hipLaunchKernelGGL((k_roi_align<false, float, GEO>), dim3((unsigned)cr_cdiv(total, 256)), dim3(256), 0, ctx->stream, py,
+                           rois, (int)R, PH, PW, (float*)out, (const float*)nullptr);
+    else
+        hipLaunchKernelGGL((k_roi_align<false, u16, GEO>), dim3((unsigned)cr_cdiv(total, 256)), dim3(256), 0, ctx->stream, py,
+                           rois, (int)R, PH, PW, (u16*)out, (const u16*)nullptr);
+    CR_LAUNCH_CHECK();
+    return CR_OK;
+}
+
+template <int GEO>
+static int launch_roi_bwd(cr_ctx* ctx, const Pyramid& py, const int* Hs, const int* Ws, const float* rois, int64_t R, int PH,
+                          int PW, const void* dout, int act_f32) {
+    const int nlev = py.nlev, C = py.C;
+    if (PH == 7 && PW == 7) {
+        int maxH = 0, maxW = 0;
+        for (int l = 0; l < nlev; ++l) { maxH = Hs[l] > maxH ? Hs[l] : maxH; maxW = Ws[l] > maxW ? Ws[l] : maxW; }
+        const size_t lds = (size_t)(maxH + maxW) * 7 * sizeof(float);
+        if (lds <= 60 * 1024) {
+            constexpr int XG_THREADS = 128;                          // 4 row phases x 32 channels
+            if (C % 256 == 0 && R * 8 < 0x7fffffff) {               // C / 8 channels per block, a multiple of a 128-B line
+                const int nt = (C / 8) * (XG_THREADS / (C / 8) > 0 ? XG_THREADS / (C / 8) : 1);
+                if (act_f32)
+                    hipLaunchKernelGGL((k_roi_align_bwd_sep<7, float, 8, GEO>), dim3((unsigned)R * 8), dim3(nt), lds, ctx->stream,
+                                       py, rois, (int)R, (const float*)dout, maxH);
+                else
+                    hipLaunchKernelGGL((k_roi_align_bwd_sep<7, u16, 8, GEO>), dim3((unsigned)R * 8), dim3(nt), lds, ctx->stream,
+                                       py, rois, (int)R, (const u16*)dout, maxH);
+            } else if (act_f32)
+                hipLaunchKernelGGL((k_roi_align_bwd_sep<7, float, 1, GEO>), dim3((unsigned)R), dim3(256), lds, ctx->stream, py,
+                                   rois, (int)R, (const float*)dout, maxH);
+            else
+                hipLaunchKernelGGL((k_roi_align_bwd_sep<7, u16, 1, GEO>), dim3((unsigned)R), dim3(256), lds, ctx->stream, py,
+                                   rois, (int)R, (const u16*)dout, maxH);
+            CR_LAUNCH_CHECK();
+            return CR_OK;
+        }
+    }
+    const int64_t total = R * PH * PW * (int64_t)C;
+    CR_CHECK_ARG(cr_cdiv(total, 256) < 0x7fffffff, "cr_roi_align_bwd: too many RoIs");
+    if (act_f32)
+        hipLaunchKernelGGL((k_roi_align_bwd<float, GEO>), dim3((unsigned)cr_cdiv(total, 256)), dim3(256), 0, ctx->stream, py,
+                           rois, (int)R, PH, PW, (const float*)dout);
+    else
+        hipLaunchKernelGGL((k_roi_align_bwd<u16, GEO>), dim3((unsigned)cr_cdiv(total, 256)), dim3(256), 0, ctx->stream, py,
+                           rois, (int)R, PH, PW, (const u16*)dout);
+    CR_LAUNCH_CHECK();
+    return CR_OK;
+}
+
+template <int GEO>
+static int launch_roi_bwd_set(cr_ctx* ctx, const Pyramid& py, const int* Hs, const int* Ws, int N, const float* rois, int64_t R,
+                              const void* dout, int act_f32) {
+    const int nlev = py.nlev, C = py.C;
+    TileMap tm;
+    tm.N = N;
+    int total = 0;
+    for (int l = 0; l < nlev; ++l) {
+        tm.base[l] = total;
+        tm.ty[l] = (Hs[l] + RT_TILE - 1) / RT_TILE;
+        tm.tx[l] = (Ws[l] + RT_TILE - 1) / RT_TILE;
+        total += N * tm.ty[l] * tm.tx[l];
+    }
+    for (int l = nlev; l <= MAX_LEVELS; ++l) tm.base[l] = total;
+    RoiExt* ext = (RoiExt*)ctx->ws;
+    if (R > 0)
+        hipLaunchKernelGGL((k_roi_bbox<7, GEO>), dim3((unsigned)cr_cdiv(R, 256)), dim3(256), 0, ctx->stream, py, rois, (int)R, N,
+                           ext);
+    const unsigned nblk = (unsigned)total * (unsigned)(C / 64);
+    if (act_f32)
+        hipLaunchKernelGGL((k_roi_bwd_tiles<7, float, GEO>), dim3(nblk), dim3(256), 0, ctx->stream, py, tm, rois, (int)R,
+                           (const float*)dout, ext);
+    else
+        hipLaunchKernelGGL((k_roi_bwd_tiles<7, u16, GEO>), dim3(nblk), dim3(256), 0, ctx->stream, py, tm, rois, (int)R,
+                           (const u16*)dout, ext);
+    CR_LAUNCH_CHECK();
     return CR_OK;
 }
 
@@ -597,15 +801,7 @@ extern "C" int cr_roi_align_fwd(cr_ctx* ctx, const void* const* feats, const int
     Pyramid py;
     int rc = fill_pyramid(py, feats, nullptr, Hs, Ws, scales, nlev, C);
     if (rc) return rc;
-    const int64_t total = R * PH * PW * (C / 8);
-    if (act_f32)
-        hipLaunchKernelGGL((k_roi_align<false, float>), dim3((unsigned)cr_cdiv(total, 256)), dim3(256), 0, ctx->stream, py,
-                           rois, (int)R, PH, PW, (float*)out, (const float*)nullptr);
-    else
-        hipLaunchKernelGGL((k_roi_align<false, u16>), dim3((unsigned)cr_cdiv(total, 256)), dim3(256), 0, ctx->stream, py,
-                           rois, (int)R, PH, PW, (u16*)out, (const u16*)nullptr);
-    CR_LAUNCH_CHECK();
-    return CR_OK;
+    return launch_roi_fwd<0>(ctx, py, rois, R, PH, PW, out, act_f32);
 }
 
 // grads: HOST array of nlev device pointers to f32 NHWC maps (accumulated with atomics; zero them first)
@@ -618,40 +814,7 @@ extern "C" int cr_roi_align_bwd(cr_ctx* ctx, float* const* grads, const int* Hs,
     Pyramid py;
     int rc = fill_pyramid(py, nullptr, grads, Hs, Ws, scales, nlev, C);
     if (rc) return rc;
-    if (PH == 7 && PW == 7) {
-        int maxH = 0, maxW = 0;
-        for (int l = 0; l < nlev; ++l) { maxH = Hs[l] > maxH ? Hs[l] : maxH; maxW = Ws[l] > maxW ? Ws[l] : maxW; }
-        const size_t lds = (size_t)(maxH + maxW) * 7 * sizeof(float);
-        if (lds <= 60 * 1024) {
-            constexpr int XG_THREADS = 128;                          // 4 row phases x 32 channels
-            if (C % 256 == 0 && R * 8 < 0x7fffffff) {               // C / 8 channels per block, a multiple of a 128-B line
-                const int nt = (C / 8) * (XG_THREADS / (C / 8) > 0 ? XG_THREADS / (C / 8) : 1);
-                if (act_f32)
-                    hipLaunchKernelGGL((k_roi_align_bwd_sep<7, float, 8>), dim3((unsigned)R * 8), dim3(nt), lds, ctx->stream, py,
-                                       rois, (int)R, (const float*)dout, maxH);
-                else
-                    hipLaunchKernelGGL((k_roi_align_bwd_sep<7, u16, 8>), dim3((unsigned)R * 8), dim3(nt), lds, ctx->stream, py,
-                                       rois, (int)R, (const u16*)dout, maxH);
-            } else if (act_f32)
-                hipLaunchKernelGGL((k_roi_align_bwd_sep<7, float, 1>), dim3((unsigned)R), dim3(256), lds, ctx->stream, py, rois,
-                                   (int)R, (const float*)dout, maxH);
-            else
-                hipLaunchKernelGGL((k_roi_align_bwd_sep<7, u16, 1>), dim3((unsigned)R), dim3(256), lds, ctx->stream, py, rois,
-                                   (int)R, (const u16*)dout, maxH);
-            CR_LAUNCH_CHECK();
-            return CR_OK;
-        }
-    }
-    const int64_t total = R * PH * PW * (int64_t)C;
-    CR_CHECK_ARG(cr_cdiv(total, 256) < 0x7fffffff, "cr_roi_align_bwd: too many RoIs");
-    if (act_f32)
-        hipLaunchKernelGGL(k_roi_align_bwd<float>, dim3((unsigned)cr_cdiv(total, 256)), dim3(256), 0, ctx->stream, py, rois,
-                           (int)R, PH, PW, (const float*)dout);
-    else
-        hipLaunchKernelGGL(k_roi_align_bwd<u16>, dim3((unsigned)cr_cdiv(total, 256)), dim3(256), 0, ctx->stream, py, rois,
-                           (int)R, PH, PW, (const u16*)dout);
-    CR_LAUNCH_CHECK();
-    return CR_OK;
+    return launch_roi_bwd<0>(ctx, py, Hs, Ws, rois, R, PH, PW, dout, act_f32);
 }
 
 // Deterministic variant of cr_roi_align_bwd: the maps are OVERWRITTEN (every pixel of every level is stored once, no zero
@@ -666,28 +829,95 @@ extern "C" int cr_roi_align_bwd_set(cr_ctx* ctx, float* const* grads, const int*
     Pyramid py;
     int rc = fill_pyramid(py, nullptr, grads, Hs, Ws, scales, nlev, C);
     if (rc) return rc;
-    TileMap tm;
-    tm.N = N;
-    int total = 0;
-    for (int l = 0; l < nlev; ++l) {
-        tm.base[l] = total;
-        tm.ty[l] = (Hs[l] + RT_TILE - 1) / RT_TILE;
-        tm.tx[l] = (Ws[l] + RT_TILE - 1) / RT_TILE;
-        total += N * tm.ty[l] * tm.tx[l];
-    }
-    for (int l = nlev; l <= MAX_LEVELS; ++l) tm.base[l] = total;
-    RoiExt* ext = (RoiExt*)ctx->ws;
-    if (R > 0)
-        hipLaunchKernelGGL(k_roi_bbox<7>, dim3((unsigned)cr_cdiv(R, 256)), dim3(256), 0, ctx->stream, py, rois, (int)R, N, ext);
-    const unsigned nblk = (unsigned)total * (unsigned)(C / 64);
-    if (act_f32)
-        hipLaunchKernelGGL((k_roi_bwd_tiles<7, float>), dim3(nblk), dim3(256), 0, ctx->stream, py, tm, rois, (int)R,
-                           (const float*)dout, ext);
-    else
-        hipLaunchKernelGGL((k_roi_bwd_tiles<7, u16>), dim3(nblk), dim3(256), 0, ctx->stream, py, tm, rois, (int)R,
-                           (const u16*)dout, ext);
-    CR_LAUNCH_CHECK();
+    return launch_roi_bwd_set<0>(ctx, py, Hs, Ws, N, rois, R, dout, act_f32);
+}
+
+// ---- the pooler's other types (pool_type 0 ROIAlignV2 | 1 ROIAlign | 2 ROIPool) and a fixed sampling ratio.  (0, ratio 0)
+// computes the bits of the default kernels above (their code plus the image-index check; the tile-owner backward is the same
+// launch); N = images in the batch: RoIs whose image index is outside [0, N) give zeros and no gradient.
+static int roi_pool_args(const char* who, int pool_type, int sampling_ratio, int N, Pyramid& py) {
+    CR_CHECK_ARG(pool_type >= 0 && pool_type <= 2, "%s: pool_type 0 ROIAlignV2 | 1 ROIAlign | 2 ROIPool", who);
+    CR_CHECK_ARG(sampling_ratio >= 0 && sampling_ratio <= 4096, "%s: sampling_ratio 0..4096", who);
+    CR_CHECK_ARG(N >= 1, "%s: N >= 1", who);
+    py.ptype = pool_type; py.sratio = sampling_ratio; py.nimg = N;
     return CR_OK;
+}
+
+// out (R,PH,PW,C) in the storage type; argmax (R,PH,PW,C) int32 for ROIPool, NULL for the RoIAlign types
+extern "C" int cr_roi_pool_fwd(cr_ctx* ctx, const void* const* feats, const int* Hs, const int* Ws, const float* scales,
+                               int nlev, int C, int N, const float* rois, int64_t R, int PH, int PW, int pool_type,
+                               int sampling_ratio, void* out, int* argmax, int act_f32) {
+    CR_CHECK_ARG(ctx && feats && Hs && Ws && scales, "cr_roi_pool_fwd: NULL pointer");
+    if (R == 0) return CR_OK;
+    CR_CHECK_ARG(rois && out && PH > 0 && PW > 0, "cr_roi_pool_fwd: bad args");
+    Pyramid py;
+    int rc = fill_pyramid(py, feats, nullptr, Hs, Ws, scales, nlev, C);
+    if (rc) return rc;
+    rc = roi_pool_args("cr_roi_pool_fwd", pool_type, sampling_ratio, N, py);
+    if (rc) return rc;
+    CR_CHECK_ARG((pool_type == 2) == (argmax != nullptr), "cr_roi_pool_fwd: argmax goes with ROIPool only");
+    if (pool_type == 2) {
+        const int64_t total = R * PH * PW * (C / 8);
+        CR_CHECK_ARG(cr_cdiv(total, 256) < 0x7fffffff, "cr_roi_pool_fwd: too many RoIs");
+        for (int l = 0; l < nlev; ++l) CR_CHECK_ARG((int64_t)Hs[l] * Ws[l] < 0x7fffffff, "cr_roi_pool_fwd: map too large");
+        if (act_f32)
+            hipLaunchKernelGGL(k_roi_pool_fwd<float>, dim3((unsigned)cr_cdiv(total, 256)), dim3(256), 0, ctx->stream, py, rois,
+                               (int)R, PH, PW, (float*)out, argmax);
+        else
+            hipLaunchKernelGGL(k_roi_pool_fwd<u16>, dim3((unsigned)cr_cdiv(total, 256)), dim3(256), 0, ctx->stream, py, rois,
+                               (int)R, PH, PW, (u16*)out, argmax);
+        CR_LAUNCH_CHECK();
+        return CR_OK;
+    }
+    if (pool_type == 0 && sampling_ratio == 0) return launch_roi_fwd<2>(ctx, py, rois, R, PH, PW, out, act_f32);
+    return launch_roi_fwd<1>(ctx, py, rois, R, PH, PW, out, act_f32);
+}
+
+// adds into grads (f32 NHWC maps, atomics): the caller zero-fills
+extern "C" int cr_roi_pool_bwd(cr_ctx* ctx, float* const* grads, const int* Hs, const int* Ws, const float* scales,
+                               int nlev, int C, int N, const float* rois, int64_t R, int PH, int PW, int pool_type,
+                               int sampling_ratio, const void* dout, const int* argmax, int act_f32) {
+    CR_CHECK_ARG(ctx && grads && Hs && Ws && scales, "cr_roi_pool_bwd: NULL pointer");
+    if (R == 0) return CR_OK;
+    CR_CHECK_ARG(rois && dout && PH > 0 && PW > 0, "cr_roi_pool_bwd: bad args");
+    Pyramid py;
+    int rc = fill_pyramid(py, nullptr, grads, Hs, Ws, scales, nlev, C);
+    if (rc) return rc;
+    rc = roi_pool_args("cr_roi_pool_bwd", pool_type, sampling_ratio, N, py);
+    if (rc) return rc;
+    CR_CHECK_ARG((pool_type == 2) == (argmax != nullptr), "cr_roi_pool_bwd: argmax goes with ROIPool only");
+    if (pool_type == 2) {
+        const int64_t total = R * PH * PW * (int64_t)C;
+        CR_CHECK_ARG(cr_cdiv(total, 256) < 0x7fffffff, "cr_roi_pool_bwd: too many RoIs");
+        if (act_f32)
+            hipLaunchKernelGGL(k_roi_pool_bwd<float>, dim3((unsigned)cr_cdiv(total, 256)), dim3(256), 0, ctx->stream, py, rois,
+                               (int)R, PH, PW, (const float*)dout, argmax);
+        else
+            hipLaunchKernelGGL(k_roi_pool_bwd<u16>, dim3((unsigned)cr_cdiv(total, 256)), dim3(256), 0, ctx->stream, py, rois,
+                               (int)R, PH, PW, (const u16*)dout, argmax);
+        CR_LAUNCH_CHECK();
+        return CR_OK;
+    }
+    if (pool_type == 0 && sampling_ratio == 0) return launch_roi_bwd<2>(ctx, py, Hs, Ws, rois, R, PH, PW, dout, act_f32);
+    return launch_roi_bwd<1>(ctx, py, Hs, Ws, rois, R, PH, PW, dout, act_f32);
+}
+
+// tile-owner backward of the RoIAlign types: overwrites every pixel, no atomics.  7 x 7 pooling, C % 64 == 0.
+extern "C" int cr_roi_pool_bwd_set(cr_ctx* ctx, float* const* grads, const int* Hs, const int* Ws, const float* scales,
+                                   int nlev, int C, int N, const float* rois, int64_t R, int PH, int PW, int pool_type,
+                                   int sampling_ratio, const void* dout, int act_f32) {
+    CR_CHECK_ARG(ctx && grads && Hs && Ws && scales, "cr_roi_pool_bwd_set: NULL pointer");
+    CR_CHECK_ARG(PH == 7 && PW == 7 && C % 64 == 0 && N >= 1, "cr_roi_pool_bwd_set: built for 7x7 pooling, C %% 64 == 0");
+    CR_CHECK_ARG(pool_type == 0 || pool_type == 1, "cr_roi_pool_bwd_set: RoIAlign types only (0 ROIAlignV2 | 1 ROIAlign)");
+    CR_CHECK_ARG(R >= 0 && R <= (int64_t)(ctx->ws_bytes / sizeof(RoiExt)) && (R == 0 || (rois && dout)),
+                 "cr_roi_pool_bwd_set: bad RoI arguments");
+    Pyramid py;
+    int rc = fill_pyramid(py, nullptr, grads, Hs, Ws, scales, nlev, C);
+    if (rc) return rc;
+    rc = roi_pool_args("cr_roi_pool_bwd_set", pool_type, sampling_ratio, N, py);
+    if (rc) return rc;
+    if (pool_type == 0 && sampling_ratio == 0) return launch_roi_bwd_set<0>(ctx, py, Hs, Ws, N, rois, R, dout, act_f32);
+    return launch_roi_bwd_set<1>(ctx, py, Hs, Ws, N, rois, R, dout, act_f32);
 }
 
 // ---------------------------------------------------------------------------

@@ -4,6 +4,7 @@ reference, on top of a detectron2 StandardROIHeads stand-in [third-party, restat
 Heavy ops: ROIAlign over the FPN pyramid (cr_roi_align_*), FC layers (library GEMM, bf16).  The per-RoI
 decode and the disentangled corner losses are small float32 torch expressions on the device (n <= 128 FG
 RoIs per image)."""
+import os
 from typing import Dict, List, Tuple
 
 import numpy as np
@@ -14,7 +15,7 @@ import torch.nn.functional as F
 from ....d2lite import (ROI_HEADS_REGISTRY, ROI_BOX_HEAD_REGISTRY, Boxes, Instances, ShapeSpec, Matcher, cat,
                         pairwise_iou, pairwise_ioa, get_event_storage)
 from .... import hipops as ops
-from ....hipops import pose_type_code, dims_func_code
+from ....hipops import pose_type_code, dims_func_code, pooler_type_code
 from ...util import math_util as util
 from ..backbone.fpn import c2_xavier_fill
 from .cube_head import build_cube_head, fc_nhwc
@@ -32,18 +33,39 @@ def build_roi_heads(cfg, input_shape, priors=None):
 
 
 class ROIPooler(nn.Module):
-    """detectron2 ROIPooler(ROIAlignV2) [third-party]: level assignment + aligned ROIAlign, fused in one kernel.
+    """detectron2 ROIPooler [third-party]: level assignment + pooling, fused in one kernel.  POOLER_TYPE ROIAlignV2 (the
+    reference's config), ROIAlign or ROIPool; POOLER_SAMPLING_RATIO 0 (adaptive grid) or a fixed number of samples per bin
+    and axis (ROIPool has no sampling grid and ignores it).  ROIAlignRotated is not built.
     Output is (R, out, out, C) bf16 -- NHWC, flattened by the heads in (h,w,c) order."""
 
     def __init__(self, output_size, scales, sampling_ratio, pooler_type):
         super().__init__()
-        assert pooler_type == "ROIAlignV2" and sampling_ratio == 0, "only the reference's pooler config is built"
+        pooler_type_code(pooler_type, sampling_ratio)          # ValueError naming the built values
+        if pooler_type == "ROIPool" and os.environ.get("CR_DETERMINISTIC", "0") not in ("", "0"):
+            raise ValueError("POOLER_TYPE ROIPool is not built for CR_DETERMINISTIC=1: its backward adds with float32 atomics, "
+                             "which fix no order; the bit-reproducible poolers are ROIAlignV2 and ROIAlign")
         self.output_size = output_size
         self.scales = tuple(scales)
+        self.pooler_type = pooler_type
+        self.sampling_ratio = sampling_ratio
+
+    def options(self):
+        """the ops.roi_align_pyramid keywords of POOLER_TYPE / POOLER_SAMPLING_RATIO, each passed only when it differs from
+        its default: the CPU stand-in of the op (oracle/cpu_backend.py) states the default pooler and has no such arguments"""
+        opt = {}
+        if self.pooler_type != "ROIAlignV2":
+            opt["pooler_type"] = self.pooler_type
+        if self.sampling_ratio != 0 and self.pooler_type != "ROIPool":
+            opt["sampling_ratio"] = self.sampling_ratio
+        return opt
+
+    def pool(self, x: List[torch.Tensor], rois):
+        """rois (R,5) [image index, x1,y1,x2,y2] over the maps x (fine -> coarse)"""
+        return ops.roi_align_pyramid(x, rois, self.scales, self.output_size, **self.options())
 
     def forward(self, x: List[torch.Tensor], box_lists: List[Boxes]):
         rois = cat([torch.cat([b.tensor.new_full((len(b), 1), i), b.tensor], 1) for i, b in enumerate(box_lists)], 0)
-        return ops.roi_align_pyramid(x, rois, self.scales, self.output_size)
+        return self.pool(x, rois)
 
 
 @ROI_BOX_HEAD_REGISTRY.register()
@@ -321,8 +343,7 @@ class ROIHeads3D(StandardROIHeads):
             scaled = self.scale_proposals([flat])[0].tensor
             idx = torch.arange(B, device=dev).repeat_interleave(D)
             rois = torch.cat([idx[:, None].float(), scaled], 1)
-            cube_features = ops.roi_align_pyramid([features[f] for f in self.in_features], rois, self.cube_pooler.scales,
-                                                  self.cube_pooler.output_size).flatten(1)
+            cube_features = self.cube_pooler.pool([features[f] for f in self.in_features], rois).flatten(1)
             raw, layout = self.cube_head.forward_fused(cube_features)
             rows = []
             for k, r, d in zip(Ks, im_scales_ratio, im_dims):
@@ -435,7 +456,7 @@ class ROIHeads3D(StandardROIHeads):
         n = sum(counts)
         idx = torch.repeat_interleave(torch.arange(len(counts), device=dev), torch.tensor(counts, device=dev))
         rois = torch.cat([idx[:, None].float(), torch.cat([b.tensor for b in boxes_scaled])], 1)
-        cube_features = ops.roi_align_pyramid(feats, rois, self.cube_pooler.scales, self.cube_pooler.output_size).flatten(1)
+        cube_features = self.cube_pooler.pool(feats, rois).flatten(1)
         raw, layout = self.cube_head.forward_fused(cube_features)
         rows = []
         for k, r, d in zip(Ks, im_scales_ratio, im_current_dims):

@@ -1353,6 +1353,18 @@ def _pyr_args(feats, scales):
 
 
 _ROI_BWD_TILES = [os.environ.get("CR_ROI_BWD_TILES", "1") == "1"]
+POOLER_TYPES = ("ROIAlignV2", "ROIAlign", "ROIPool")       # codes 0, 1, 2 of cr_roi_pool_*
+
+
+def pooler_type_code(pooler_type, sampling_ratio=0):
+    """(POOLER_TYPE, POOLER_SAMPLING_RATIO) -> the (pool_type, sampling_ratio) codes of cr_roi_pool_*"""
+    if pooler_type not in POOLER_TYPES:
+        raise ValueError("POOLER_TYPE %r is not built: the built types are %s" % (pooler_type, ", ".join(POOLER_TYPES)))
+    if not isinstance(sampling_ratio, int) or isinstance(sampling_ratio, bool) or sampling_ratio < 0:
+        raise ValueError("POOLER_SAMPLING_RATIO %r is not built: 0 (adaptive grid) or a positive integer, with POOLER_TYPE "
+                         "one of %s" % (sampling_ratio, ", ".join(POOLER_TYPES)))
+    code = POOLER_TYPES.index(pooler_type)
+    return code, (0 if code == 2 else int(sampling_ratio))     # ROIPool has no sampling grid
 
 
 class _ROIAlign(torch.autograd.Function):
@@ -1364,7 +1376,7 @@ class _ROIAlign(torch.autograd.Function):
       * a fresh zero-filled buffer returned to autograd."""
 
     @staticmethod
-    def forward(ctx, rois, scales, out_size, slots, *feats):
+    def forward(ctx, rois, scales, out_size, slots, geo, *feats):
         _need_cuda(rois, "rois")
         C = feats[0].shape[3]
         R = rois.shape[0]
@@ -1373,8 +1385,16 @@ class _ROIAlign(torch.autograd.Function):
         out = torch.empty((R, out_size, out_size, C), dtype=dt, device=rois.device)
         n, ptrs, Hs, Ws, sc, cast = _pyr_args(feats, scales)
         rois = rois.contiguous()
-        _lib.call("cr_roi_align_fwd", cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, rois, R, out_size, out_size, out,
-                  _af(out))
+        argmax = None
+        if geo == (0, 0):
+            _lib.call("cr_roi_align_fwd", cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, rois, R, out_size, out_size, out,
+                      _af(out))
+        else:
+            # ROIPool keeps the winning pixel of every output for its backward
+            argmax = torch.empty((R, out_size, out_size, C), dtype=torch.int32, device=rois.device) if geo[0] == 2 else None
+            _lib.call("cr_roi_pool_fwd", cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, int(feats[0].shape[0]), rois, R,
+                      out_size, out_size, geo[0], geo[1], out, argmax, _af(out))
+        ctx.geo, ctx.argmax = geo, argmax
         ctx.cfg = (scales, out_size, [tuple(f.shape) for f in feats], dt)
         ctx.slots = slots
         # claimed (popped): a second RoIAlign over the same maps takes the ordinary path and autograd adds the two
@@ -1390,7 +1410,8 @@ class _ROIAlign(torch.autograd.Function):
         dsts = ctx.dsts
         # tile-owner kernel (cr_roi_align_bwd_set): writes every pixel of every level once, no atomics, bit-reproducible,
         # and the maps need no zero fill.  CR_ROI_BWD_TILES=0: the separable atomic kernel (A/B).
-        tiles = _ROI_BWD_TILES[0] and out_size == 7 and C % 64 == 0 and len({s[0] for s in shapes}) == 1
+        geo = ctx.geo
+        tiles = _ROI_BWD_TILES[0] and out_size == 7 and C % 64 == 0 and len({s[0] for s in shapes}) == 1 and geo[0] != 2
         if all(d is not None and d.dtype == f32 and tuple(d.shape) == tuple(s) for d, s in zip(dsts, shapes)):
             grads = dsts
             if not tiles:
@@ -1405,7 +1426,14 @@ class _ROIAlign(torch.autograd.Function):
                 off += n_
         n, ptrs, Hs, Ws, sc, cast = _pyr_args(grads, scales)
         dout = dout.to(dt).contiguous()
-        if tiles:
+        if geo != (0, 0):
+            if tiles:
+                _lib.call("cr_roi_pool_bwd_set", cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, int(shapes[0][0]), rois,
+                          rois.shape[0], out_size, out_size, geo[0], geo[1], dout, _af(dout))
+            else:
+                _lib.call("cr_roi_pool_bwd", cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, int(shapes[0][0]), rois,
+                          rois.shape[0], out_size, out_size, geo[0], geo[1], dout, ctx.argmax, _af(dout))
+        elif tiles:
             _lib.call("cr_roi_align_bwd_set", cast(ptrs), cast(Hs), cast(Ws), cast(sc), n, C, int(shapes[0][0]), rois,
                       rois.shape[0], out_size, out_size, dout, _af(dout))
         else:
@@ -1418,7 +1446,7 @@ class _ROIAlign(torch.autograd.Function):
                 _slot_put(slot, g)
                 g = None
             res.append(g)
-        return (None, None, None, None) + tuple(res)
+        return (None, None, None, None, None) + tuple(res)
 
 
 class _SharedPrefix(torch.autograd.Function):
@@ -1447,10 +1475,13 @@ def shared_prefix(pooled, B, S, kf):
     return _SharedPrefix.apply(pooled, B, S, kf)
 
 
-def roi_align_pyramid(feats, rois, scales, out_size):
-    """feats: list of NHWC maps (fine -> coarse) in the activation dtype; rois (R,5) f32 [batch,x1,y1,x2,y2]."""
+def roi_align_pyramid(feats, rois, scales, out_size, *, pooler_type="ROIAlignV2", sampling_ratio=0):
+    """feats: list of NHWC maps (fine -> coarse) in the activation dtype; rois (R,5) f32 [batch,x1,y1,x2,y2].
+    pooler_type / sampling_ratio: POOLER_TYPES and the samples per bin and axis (0: adaptive); the defaults launch
+    cr_roi_align_*, every other pair cr_roi_pool_*."""
+    geo = pooler_type_code(pooler_type, sampling_ratio)
     slots = tuple(_slot_register(f, False) for f in feats)
-    return _ROIAlign.apply(rois.to(f32), tuple(scales), out_size, slots, *feats)
+    return _ROIAlign.apply(rois.to(f32), tuple(scales), out_size, slots, geo, *feats)
 
 
 # --------------------------------------------------------------------------

@@ -435,6 +435,22 @@ int cr_roi_align_bwd(cr_ctx* ctx, float* const* grads, const int* Hs, const int*
 int cr_roi_align_bwd_set(cr_ctx* ctx, float* const* grads, const int* Hs, const int* Ws, const float* scales,
                          int nlev, int C, int N, const float* rois, int64_t R, int PH, int PW, const void* dout,
                          int act_f32);
+/* The pooler's other types and a fixed sampling ratio (MODEL.ROI_{BOX,CUBE}_HEAD.POOLER_TYPE / POOLER_SAMPLING_RATIO,
+ * cubercnn/config/config.py:43-45, read at roi_heads.py:2071-2080; pooled at roi_heads.py:2178,2273).  torchvision roi_align /
+ * roi_pool and detectron2 ROIPooler restated.  pool_type 0 ROIAlignV2 | 1 ROIAlign (no half-pixel offset, extent >= 1 px) |
+ * 2 ROIPool (quantised max pooling; sampling_ratio ignored).  sampling_ratio > 0: that many samples per bin and axis, 0:
+ * ceil(extent / P).  (0, 0) computes the bits of cr_roi_align_*.  N = images in the batch: RoIs with rois[:,0] outside
+ * [0,N) give zeros and no gradient.  argmax (R,PH,PW,C) int32, y*W+x on the RoI's level or -1: ROIPool only, else NULL.
+ * cr_roi_pool_bwd ADDS (atomics; zero first); cr_roi_pool_bwd_set OVERWRITES every pixel (RoIAlign types, 7x7, C % 64 == 0). */
+int cr_roi_pool_fwd(cr_ctx* ctx, const void* const* feats, const int* Hs, const int* Ws, const float* scales,
+                    int nlev, int C, int N, const float* rois, int64_t R, int PH, int PW, int pool_type,
+                    int sampling_ratio, void* out, int* argmax, int act_f32);
+int cr_roi_pool_bwd(cr_ctx* ctx, float* const* grads, const int* Hs, const int* Ws, const float* scales,
+                    int nlev, int C, int N, const float* rois, int64_t R, int PH, int PW, int pool_type,
+                    int sampling_ratio, const void* dout, const int* argmax, int act_f32);
+int cr_roi_pool_bwd_set(cr_ctx* ctx, float* const* grads, const int* Hs, const int* Ws, const float* scales,
+                        int nlev, int C, int N, const float* rois, int64_t R, int PH, int PW, int pool_type,
+                        int sampling_ratio, const void* dout, int act_f32);
 /* batched NMS over G independent groups; boxes (G,maxn,4) sorted by descending score per group, counts (G)
  * int32; keep (G,maxn) uint8; mask_ws: G*maxn*ceil(maxn/64)*8 bytes.  fast_rcnn.py:105, detectron2 RPN. */
 int cr_nms_grouped(cr_ctx* ctx, const float* boxes, const int* counts, int G, int maxn, float thresh,

@@ -5,7 +5,9 @@
 //
 // Reference code paths restated here (paths into the reference tree):
 //   cubercnn/modeling/proposal_generator/rpn.py:41-110   RPNWithIgnore.label_and_sample_anchors (+ ignore regions)
-//   cubercnn/modeling/proposal_generator/rpn.py:129-273  losses, "IoUness" objectness, uncertainty-weighted L1
+//   cubercnn/modeling/proposal_generator/rpn.py:129-273  losses: "IoUness" objectness with IoU-weighted smooth L1, or plain
+//                                                         objectness ("none") with smooth L1 / giou / diou / ciou
+//   cubercnn/modeling/roi_heads/fast_rcnn.py:145-260      FastRCNNOutputs.losses (smooth L1 with beta, class-agnostic deltas)
 //   cubercnn/modeling/proposal_generator/rpn.py:275-328  subsample_labels (IoU-weighted multinomial sampling)
 //   cubercnn/modeling/roi_heads/roi_heads.py:2773-2840   ROIHeads3D.label_and_sample_proposals
 //   detectron2 Matcher / Box2BoxTransform / find_top_rpn_proposals [third-party, restated in 3dod_amd/d2lite]
@@ -299,18 +301,113 @@ extern "C" int cr_rpn_scatter(cr_ctx* ctx, const int64_t* pos_idx, const float* 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// 5. RPN losses and their gradients in one pass (rpn.py:129-273, "IoUness" objectness, smooth_l1 beta 0 = L1):
+// 5. RPN losses and their gradients in one pass (rpn.py:129-273), a template over the option set:
+//    OBJ 0 = any MODEL.RPN.OBJECTNESS_UNCERTAINTY but "none" (rpn.py:206-273, "IoUness"):
 //      t = IoU(anchor, matched gt) for positives, else 0
-//      loss_cls = sum BCEWithLogits(logit, t) * t,   loss_loc = sum_pos |delta - target|_1 * t
+//      loss_cls = sum BCEWithLogits(logit, t) * t,   loss_loc = sum_pos smooth_l1(delta - target) * t
+//    OBJ 1 = "none" (rpn.py:181-197): loss_cls = sum_{label >= 0} BCEWithLogits(logit, label), loss_loc = sum_pos reg
+//    REG 0 = smooth_l1 with beta < 1e-5 (L1), 1 = smooth_l1 with beta, 2 / 3 / 4 = giou / diou / ciou of the decoded box
+//    (detectron2 _dense_box_regression_loss + fvcore giou_loss / diou_loss / ciou_loss [third-party, parity unpinned]).
+//    <0, 0> is the default configuration: its arithmetic and order of operations are those of the untemplated kernel.
 //    sums[6] = [loss_cls, loss_loc, n_pos, n_neg, sum sigmoid(logit) over pos, sum sigmoid(logit) over non-pos]
 //    (two-stage, fixed-order reduction: bitwise reproducible);  dlogits (B,A), ddeltas (B,A,4) unscaled.
 // ---------------------------------------------------------------------------------------------------------------
 #define LOSS_NV 6
+#define REG_L1 0
+#define REG_BETA 1
+#define REG_GIOU 2
+#define REG_DIOU 3
+#define REG_CIOU 4
+
+// smooth L1 (fvcore smooth_l1_loss, beta >= 1e-5): value and derivative of one element
+__device__ __forceinline__ float sl1_beta(float e, float beta, float& de) {
+    const float a = fabsf(e);
+    if (a < beta) { de = e / beta; return 0.5f * e * e / beta; }
+    de = e > 0.f ? 1.f : -1.f;
+    return a - 0.5f * beta;
+}
+
+// giou / diou / ciou loss of the predicted box p against g (eps 1e-7) and its gradient gb = d loss / d (x1, y1, x2, y2) of p.
+//   inter = overlap area (0 unless both overlaps > 0), union = area_p + area_g - inter, iou = inter / (union + eps), c = enclosing box
+//   giou: 1 - iou + (area_c - union) / (area_c + eps)
+//   diou: 1 - iou + dist / diag, dist = squared centre distance, diag = wc^2 + hc^2 + eps
+//   ciou: diou + alpha v, v = (4 / pi^2) (atan(wg / hg) - atan(wp / hp))^2, alpha = v / (1 - iou + v + eps) held constant
+// max / min pass their gradient to the argument they select.
+template <int REG>
+__device__ __forceinline__ float iou_family_loss(const Box& p, const Box& g, float gb[4]) {
+    const float eps = 1e-7f;
+    const float wp = p.x2 - p.x1, hp = p.y2 - p.y1, wg = g.x2 - g.x1, hg = g.y2 - g.y1;
+    const float wi = fminf(p.x2, g.x2) - fmaxf(p.x1, g.x1), hi = fminf(p.y2, g.y2) - fmaxf(p.y1, g.y1);
+    const bool ov = wi > 0.f && hi > 0.f;
+    const float inter = ov ? wi * hi : 0.f;
+    // which corner of p is the selected one in the intersection (inner) and in the enclosing box (outer)
+    const bool in_x1 = p.x1 > g.x1, in_y1 = p.y1 > g.y1, in_x2 = p.x2 < g.x2, in_y2 = p.y2 < g.y2;
+    const bool out_x1 = p.x1 < g.x1, out_y1 = p.y1 < g.y1, out_x2 = p.x2 > g.x2, out_y2 = p.y2 > g.y2;
+    float dI[4], dU[4];
+    dI[0] = (ov && in_x1) ? -hi : 0.f;
+    dI[1] = (ov && in_y1) ? -wi : 0.f;
+    dI[2] = (ov && in_x2) ? hi : 0.f;
+    dI[3] = (ov && in_y2) ? wi : 0.f;
+    dU[0] = -hp - dI[0];
+    dU[1] = -wp - dI[1];
+    dU[2] = hp - dI[2];
+    dU[3] = wp - dI[3];
+    const float uni = wp * hp + wg * hg - inter;
+    const float ue = uni + eps;
+    const float iou = inter / ue;
+    const float inv_ue2 = 1.f / (ue * ue);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) gb[k] = -(dI[k] * ue - inter * dU[k]) * inv_ue2;      // d(1 - iou)
+    const float wc = fmaxf(p.x2, g.x2) - fminf(p.x1, g.x1), hc = fmaxf(p.y2, g.y2) - fminf(p.y1, g.y1);
+    float loss = 1.f - iou;
+    if (REG == REG_GIOU) {
+        const float ac = wc * hc, ace = ac + eps;
+        float dC[4];
+        dC[0] = out_x1 ? -hc : 0.f;
+        dC[1] = out_y1 ? -wc : 0.f;
+        dC[2] = out_x2 ? hc : 0.f;
+        dC[3] = out_y2 ? wc : 0.f;
+        loss += (ac - uni) / ace;
+        const float inv_ace2 = 1.f / (ace * ace);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gb[k] += ((dC[k] - dU[k]) * ace - (ac - uni) * dC[k]) * inv_ace2;
+    } else {
+        const float diag = wc * wc + hc * hc + eps;
+        const float ddx = 0.5f * (p.x1 + p.x2) - 0.5f * (g.x1 + g.x2), ddy = 0.5f * (p.y1 + p.y2) - 0.5f * (g.y1 + g.y2);
+        const float dist = ddx * ddx + ddy * ddy;
+        float dG[4];
+        dG[0] = out_x1 ? -2.f * wc : 0.f;
+        dG[1] = out_y1 ? -2.f * hc : 0.f;
+        dG[2] = out_x2 ? 2.f * wc : 0.f;
+        dG[3] = out_y2 ? 2.f * hc : 0.f;
+        const float dD[4] = {ddx, ddy, ddx, ddy};
+        loss += dist / diag;
+        const float inv_d2 = 1.f / (diag * diag);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gb[k] += (dD[k] * diag - dist * dG[k]) * inv_d2;
+        if (REG == REG_CIOU) {
+            const float c4 = 0.40528473456935108578f;                      // 4 / pi^2
+            const float da = atanf(wg / hg) - atanf(wp / hp);
+            const float v = c4 * da * da;
+            const float alpha = v / (1.f - iou + v + eps);
+            loss += alpha * v;
+            // d atan(wp / hp) = (hp dwp - wp dhp) / (wp^2 + hp^2)
+            const float q = alpha * (-2.f * c4 * da) / (wp * wp + hp * hp);
+            const float gw = q * hp, gh = -q * wp;                             // alpha dv/dwp, alpha dv/dhp
+            gb[0] -= gw; gb[2] += gw;
+            gb[1] -= gh; gb[3] += gh;
+        }
+    }
+    return loss;
+}
+
+template <int OBJ, int REG>
 __global__ __launch_bounds__(256) void k_rpn_loss(const float* __restrict__ logits, const float* __restrict__ deltas,
                                                   const float* __restrict__ anchors, const int* __restrict__ labels,
                                                   const int* __restrict__ midx, const float* __restrict__ gtb, int B, int A,
-                                                  int G, float wx, float wy, float ww, float wh, float* __restrict__ partial,
-                                                  float* __restrict__ dlogits, float* __restrict__ ddeltas) {
+                                                  int G, float wx, float wy, float ww, float wh, float beta, float scale_clamp,
+                                                  float* __restrict__ partial, float* __restrict__ dlogits,
+                                                  float* __restrict__ ddeltas) {
     const int b = blockIdx.y, a = blockIdx.x * 256 + threadIdx.x;
     float v[LOSS_NV] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (a < A) {
@@ -320,22 +417,52 @@ __global__ __launch_bounds__(256) void k_rpn_loss(const float* __restrict__ logi
         const float sig = 1.f / (1.f + expf(-x));
         float dl = 0.f;
         float4 dd = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (OBJ == 1 && lab >= 0) {                              // plain objectness: the target is the label
+            const float t = lab == 1 ? 1.f : 0.f;
+            v[0] = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+            dl = sig - t;
+        }
         if (lab == 1) {
             const Box an = ldbox(anchors + (size_t)a * 4);
             const Box g = ldbox(gtb + ((size_t)b * G + midx[i]) * 4);
-            const float inter = box_inter(an, g);
-            const float t = inter / (box_area(an) + box_area(g) - inter);
-            const float bce = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
-            v[0] = bce * t;
-            dl = (sig - t) * t;
+            float t = 1.f;                                       // weight of the localization term
+            if (OBJ == 0) {
+                const float inter = box_inter(an, g);
+                t = inter / (box_area(an) + box_area(g) - inter);
+                const float bce = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+                v[0] = bce * t;
+                dl = (sig - t) * t;
+            }
             const float sw = an.x2 - an.x1, sh = an.y2 - an.y1, sx = an.x1 + 0.5f * sw, sy = an.y1 + 0.5f * sh;
-            const float tw = g.x2 - g.x1, th = g.y2 - g.y1, tx = g.x1 + 0.5f * tw, ty = g.y1 + 0.5f * th;
             const float4 d = *reinterpret_cast<const float4*>(deltas + i * 4);
-            const float e0 = d.x - wx * (tx - sx) / sw, e1 = d.y - wy * (ty - sy) / sh;
-            const float e2 = d.z - ww * logf(tw / sw), e3 = d.w - wh * logf(th / sh);
-            v[1] = (((fabsf(e0) + fabsf(e1)) + fabsf(e2)) + fabsf(e3)) * t;
-            auto sgn = [](float z) { return z > 0.f ? 1.f : (z < 0.f ? -1.f : 0.f); };
-            dd = make_float4(sgn(e0) * t, sgn(e1) * t, sgn(e2) * t, sgn(e3) * t);
+            if (REG == REG_L1 || REG == REG_BETA) {
+                const float tw = g.x2 - g.x1, th = g.y2 - g.y1, tx = g.x1 + 0.5f * tw, ty = g.y1 + 0.5f * th;
+                const float e0 = d.x - wx * (tx - sx) / sw, e1 = d.y - wy * (ty - sy) / sh;
+                const float e2 = d.z - ww * logf(tw / sw), e3 = d.w - wh * logf(th / sh);
+                if (REG == REG_L1) {
+                    v[1] = (((fabsf(e0) + fabsf(e1)) + fabsf(e2)) + fabsf(e3)) * t;
+                    auto sgn = [](float z) { return z > 0.f ? 1.f : (z < 0.f ? -1.f : 0.f); };
+                    dd = make_float4(sgn(e0) * t, sgn(e1) * t, sgn(e2) * t, sgn(e3) * t);
+                } else {
+                    float g0, g1, g2, g3;
+                    const float l0 = sl1_beta(e0, beta, g0), l1 = sl1_beta(e1, beta, g1);
+                    const float l2 = sl1_beta(e2, beta, g2), l3 = sl1_beta(e3, beta, g3);
+                    v[1] = (((l0 + l1) + l2) + l3) * t;
+                    dd = make_float4(g0 * t, g1 * t, g2 * t, g3 * t);
+                }
+            } else {
+                // Box2BoxTransform.apply_deltas of the anchor; dw / dh clamped at scale_clamp (no gradient where the clamp is active)
+                const float dwr = d.z / ww, dhr = d.w / wh;
+                const float dw = fminf(dwr, scale_clamp), dh = fminf(dhr, scale_clamp);
+                const float pcx = (d.x / wx) * sw + sx, pcy = (d.y / wy) * sh + sy, pw = expf(dw) * sw, ph = expf(dh) * sh;
+                const Box p = Box{pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph};
+                float gb[4];
+                v[1] = iou_family_loss<REG>(p, g, gb);
+                // x1 = pcx - pw / 2, x2 = pcx + pw / 2;  d pcx / d delta_x = sw / wx,  d pw / d delta_w = pw / ww
+                dd = make_float4((gb[0] + gb[2]) * (sw / wx), (gb[1] + gb[3]) * (sh / wy),
+                                 dwr <= scale_clamp ? 0.5f * (gb[2] - gb[0]) * (pw / ww) : 0.f,
+                                 dhr <= scale_clamp ? 0.5f * (gb[3] - gb[1]) * (ph / wh) : 0.f);
+            }
             v[2] = 1.f;
             v[4] = sig;
         } else {
@@ -384,8 +511,43 @@ extern "C" int cr_rpn_loss(cr_ctx* ctx, const float* logits, const float* deltas
                  dlogits && ddeltas, "cr_rpn_loss: NULL pointer");
     CR_CHECK_ARG(B > 0 && A > 0 && G > 0, "cr_rpn_loss: bad sizes");
     const int nb = (int)cr_cdiv(A, 256);
-    hipLaunchKernelGGL(k_rpn_loss, dim3(nb, B), dim3(256), 0, ctx->stream, logits, deltas, anchors, labels, matched_idx,
-                       gt_boxes, B, A, G, weights4[0], weights4[1], weights4[2], weights4[3], partial_ws, dlogits, ddeltas);
+    hipLaunchKernelGGL((k_rpn_loss<0, REG_L1>), dim3(nb, B), dim3(256), 0, ctx->stream, logits, deltas, anchors, labels,
+                       matched_idx, gt_boxes, B, A, G, weights4[0], weights4[1], weights4[2], weights4[3], 0.f, 0.f, partial_ws,
+                       dlogits, ddeltas);
+    CR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, partial_ws, nb * B, LOSS_NV, sums6);
+    CR_LAUNCH_CHECK();
+    return CR_OK;
+}
+
+// the other option sets of the same pass.  objectness: 0 = IoU-weighted (every OBJECTNESS_UNCERTAINTY but "none"), 1 = "none";
+// reg_type: 0 smooth_l1 (L1 when beta < 1e-5), 1 giou, 2 diou, 3 ciou (1-3 with objectness 1 only: rpn.py:271 raises otherwise).
+extern "C" int cr_rpn_loss_opt(cr_ctx* ctx, const float* logits, const float* deltas, const float* anchors, const int* labels,
+                               const int* matched_idx, const float* gt_boxes, int B, int A, int G, const float* weights4,
+                               int objectness, int reg_type, float beta, float scale_clamp, float* partial_ws, float* sums6,
+                               float* dlogits, float* ddeltas) {
+    CR_CHECK_ARG(ctx && logits && deltas && anchors && labels && matched_idx && gt_boxes && weights4 && partial_ws && sums6 &&
+                 dlogits && ddeltas, "cr_rpn_loss_opt: NULL pointer");
+    CR_CHECK_ARG(B > 0 && A > 0 && G > 0, "cr_rpn_loss_opt: bad sizes");
+    CR_CHECK_ARG((objectness == 0 || objectness == 1) && reg_type >= 0 && reg_type <= 3 && beta >= 0.f,
+                 "cr_rpn_loss_opt: objectness in {0, 1}, reg_type in 0..3, beta >= 0 required");
+    CR_CHECK_ARG(objectness == 1 || reg_type == 0, "cr_rpn_loss_opt: the IoU-weighted objectness is built with smooth_l1 only");
+    const int nb = (int)cr_cdiv(A, 256);
+    const int reg = reg_type == 0 ? (beta < 1e-5f ? REG_L1 : REG_BETA) : reg_type + 1;
+#define CR_RPN_LOSS_CASE(O, R)                                                                                                  \
+    if (objectness == O && reg == R)                                                                                            \
+        hipLaunchKernelGGL((k_rpn_loss<O, R>), dim3(nb, B), dim3(256), 0, ctx->stream, logits, deltas, anchors, labels,         \
+                           matched_idx, gt_boxes, B, A, G, weights4[0], weights4[1], weights4[2], weights4[3], beta, scale_clamp, \
+                           partial_ws, dlogits, ddeltas)
+    CR_RPN_LOSS_CASE(0, REG_L1);
+    else CR_RPN_LOSS_CASE(0, REG_BETA);
+    else CR_RPN_LOSS_CASE(1, REG_L1);
+    else CR_RPN_LOSS_CASE(1, REG_BETA);
+    else CR_RPN_LOSS_CASE(1, REG_GIOU);
+    else CR_RPN_LOSS_CASE(1, REG_DIOU);
+    else CR_RPN_LOSS_CASE(1, REG_CIOU);
+    else CR_CHECK_ARG(false, "cr_rpn_loss_opt: no kernel for objectness %d, reg_type %d", objectness, reg_type);
+#undef CR_RPN_LOSS_CASE
     CR_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, partial_ws, nb * B, LOSS_NV, sums6);
     CR_LAUNCH_CHECK();
@@ -509,16 +671,20 @@ extern "C" int cr_roi_compact(cr_ctx* ctx, const int64_t* fg_idx, const float* f
 
 // ---------------------------------------------------------------------------------------------------------------
 // 8. Fast R-CNN losses on the padded sample (fast_rcnn.py:145-194): softmax cross-entropy over K+1 classes on the
-//    valid rows, L1 (smooth_l1, beta 0) box regression on the foreground rows' own class, both as sums (the caller
+//    valid rows, smooth_l1 box regression on the foreground rows' own class, both as sums (the caller
 //    divides by the number of valid rows), with gradients and the decoded boxes of the sampled class.  One wave / row.
-//    sums3 = [sum ce, sum l1, n_valid];  dscores (N,K+1), ddeltas (N,K*4), pred (N,4).
+//    sums3 = [sum ce, sum l1, n_valid];  dscores (N,K+1), ddeltas (N,KD*4), pred (N,4).
+//    A template over ROI_BOX_HEAD.SMOOTH_L1_BETA (BETA false: beta < 1e-5, L1; fast_rcnn.py:245-252) and CLS_AGNOSTIC_BBOX_REG
+//    (AGN true: deltas (N,4), KD = 1, every row reads and writes its one box; fast_rcnn.py:207-208); <false, false> is the
+//    default configuration with the arithmetic and order of operations of the untemplated kernel.
 // ---------------------------------------------------------------------------------------------------------------
+template <bool BETA, bool AGN>
 __global__ __launch_bounds__(256) void k_box_loss(const float* __restrict__ scores, const float* __restrict__ deltas,
                                                   const unsigned char* __restrict__ valid, const int64_t* __restrict__ cls,
                                                   const float* __restrict__ pboxes, const int64_t* __restrict__ gt_idx,
                                                   const float* __restrict__ gtb, int N, int S, int G, int K, float wx, float wy,
-                                                  float ww, float wh, float scale_clamp, float* __restrict__ partial,
-                                                  float* __restrict__ dscores, float* __restrict__ ddeltas,
+                                                  float ww, float wh, float scale_clamp, float beta,
+                                                  float* __restrict__ partial, float* __restrict__ dscores, float* __restrict__ ddeltas,
                                                   float* __restrict__ pred) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wave;
@@ -543,14 +709,15 @@ __global__ __launch_bounds__(256) void k_box_loss(const float* __restrict__ scor
             dscores[(size_t)row * C + j] = ok ? (p - (j == tcls ? 1.f : 0.f)) : 0.f;
         }
         const bool fg = ok && c0 >= 0 && c0 < K;
-        const int kcls = tcls < K ? tcls : K - 1;
-        float* dr = ddeltas + (size_t)row * K * 4;
-        for (int j = lane; j < K * 4; j += 64) dr[j] = 0.f;
+        const int KD = AGN ? 1 : K;
+        const int kcls = AGN ? 0 : (tcls < K ? tcls : K - 1);
+        float* dr = ddeltas + (size_t)row * KD * 4;
+        for (int j = lane; j < KD * 4; j += 64) dr[j] = 0.f;
         if (lane == 0) {
             v[0] = ok ? lse - sr[tcls] : 0.f;
             v[2] = ok ? 1.f : 0.f;
             const Box pb = ldbox(pboxes + (size_t)row * 4);
-            const float4 d = *reinterpret_cast<const float4*>(deltas + ((size_t)row * K + kcls) * 4);
+            const float4 d = *reinterpret_cast<const float4*>(deltas + ((size_t)row * KD + kcls) * 4);
             const float sw = pb.x2 - pb.x1, sh = pb.y2 - pb.y1, sx = pb.x1 + 0.5f * sw, sy = pb.y1 + 0.5f * sh;
             if (fg) {
                 const int b = row / S;
@@ -558,9 +725,17 @@ __global__ __launch_bounds__(256) void k_box_loss(const float* __restrict__ scor
                 const float tw = g.x2 - g.x1, th = g.y2 - g.y1, tx = g.x1 + 0.5f * tw, ty = g.y1 + 0.5f * th;
                 const float e0 = d.x - wx * (tx - sx) / sw, e1 = d.y - wy * (ty - sy) / sh;
                 const float e2 = d.z - ww * logf(tw / sw), e3 = d.w - wh * logf(th / sh);
-                v[1] = ((fabsf(e0) + fabsf(e1)) + fabsf(e2)) + fabsf(e3);
-                auto sgn = [](float z) { return z > 0.f ? 1.f : (z < 0.f ? -1.f : 0.f); };
-                *reinterpret_cast<float4*>(dr + kcls * 4) = make_float4(sgn(e0), sgn(e1), sgn(e2), sgn(e3));
+                if (!BETA) {
+                    v[1] = ((fabsf(e0) + fabsf(e1)) + fabsf(e2)) + fabsf(e3);
+                    auto sgn = [](float z) { return z > 0.f ? 1.f : (z < 0.f ? -1.f : 0.f); };
+                    *reinterpret_cast<float4*>(dr + kcls * 4) = make_float4(sgn(e0), sgn(e1), sgn(e2), sgn(e3));
+                } else {
+                    float g0, g1, g2, g3;
+                    const float l0 = sl1_beta(e0, beta, g0), l1 = sl1_beta(e1, beta, g1);
+                    const float l2 = sl1_beta(e2, beta, g2), l3 = sl1_beta(e3, beta, g3);
+                    v[1] = ((l0 + l1) + l2) + l3;
+                    *reinterpret_cast<float4*>(dr + kcls * 4) = make_float4(g0, g1, g2, g3);
+                }
             }
             // Box2BoxTransform.apply_deltas of the row's own class
             const float dx = d.x / wx, dy = d.y / wy, dw = fminf(d.z / ww, scale_clamp), dh = fminf(d.w / wh, scale_clamp);
@@ -588,9 +763,38 @@ extern "C" int cr_box_loss(cr_ctx* ctx, const float* scores, const float* deltas
     if (N == 0) return CR_OK;
     CR_CHECK_ARG(K > 0 && G > 0, "cr_box_loss: bad sizes");
     const int nb = (int)cr_cdiv(N, 4);
-    hipLaunchKernelGGL(k_box_loss, dim3(nb), dim3(256), 0, ctx->stream, scores, deltas, valid, cls, prop_boxes, gt_idx, gt_boxes,
-                       N, S, G, K, weights4[0], weights4[1], weights4[2], weights4[3], scale_clamp, partial_ws, dscores, ddeltas,
-                       pred);
+    hipLaunchKernelGGL((k_box_loss<false, false>), dim3(nb), dim3(256), 0, ctx->stream, scores, deltas, valid, cls, prop_boxes,
+                       gt_idx, gt_boxes, N, S, G, K, weights4[0], weights4[1], weights4[2], weights4[3], scale_clamp, 0.f, partial_ws,
+                       dscores, ddeltas, pred);
+    CR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, partial_ws, nb, 3, sums3);
+    CR_LAUNCH_CHECK();
+    return CR_OK;
+}
+
+// the other option sets of the same pass: smooth_l1 beta (L1 when < 1e-5) and class-agnostic regression (deltas / ddeltas (B*S,4)).
+extern "C" int cr_box_loss_opt(cr_ctx* ctx, const float* scores, const float* deltas, const unsigned char* valid,
+                               const int64_t* cls, const float* prop_boxes, const int64_t* gt_idx, const float* gt_boxes, int B,
+                               int S, int G, int K, const float* weights4, float scale_clamp, float beta, int cls_agnostic,
+                               float* partial_ws, float* sums3, float* dscores, float* ddeltas, float* pred) {
+    CR_CHECK_ARG(ctx && scores && deltas && valid && cls && prop_boxes && gt_idx && gt_boxes && weights4 && partial_ws && sums3 &&
+                 dscores && ddeltas && pred, "cr_box_loss_opt: NULL pointer");
+    const int N = B * S;
+    if (N == 0) return CR_OK;
+    CR_CHECK_ARG(K > 0 && G > 0 && beta >= 0.f, "cr_box_loss_opt: bad sizes or beta < 0");
+    const int nb = (int)cr_cdiv(N, 4);
+    const bool sl1 = !(beta < 1e-5f), agn = cls_agnostic != 0;
+#define CR_BOX_LOSS_CASE(BT, AG)                                                                                                \
+    if (sl1 == BT && agn == AG)                                                                                                 \
+        hipLaunchKernelGGL((k_box_loss<BT, AG>), dim3(nb), dim3(256), 0, ctx->stream, scores, deltas, valid, cls, prop_boxes,   \
+                           gt_idx, gt_boxes, N, S, G, K, weights4[0], weights4[1], weights4[2], weights4[3], scale_clamp, beta, \
+                           partial_ws, dscores, ddeltas, pred)
+    CR_BOX_LOSS_CASE(false, false);
+    else CR_BOX_LOSS_CASE(false, true);
+    else CR_BOX_LOSS_CASE(true, false);
+    else CR_BOX_LOSS_CASE(true, true);
+    else CR_CHECK_ARG(false, "cr_box_loss_opt: no kernel for beta %g, cls_agnostic %d", (double)beta, cls_agnostic);
+#undef CR_BOX_LOSS_CASE
     CR_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, ctx->stream, partial_ws, nb, 3, sums3);
     CR_LAUNCH_CHECK();

@@ -124,20 +124,24 @@ def matched_boxes(gt: GTBatch, midx):
 
 
 def rpn_losses(rpn, anchors, logits, deltas, labels, midx, gt: GTBatch):
-    """RPNWithIgnore.losses + _dense_box_regression_loss_with_uncertainty (rpn.py:129-273), "IoUness" objectness.
-    logits (B,A), deltas (B,A,4); one fused kernel computes both sums, the logging counters and the gradients."""
-    assert rpn.objectness_uncertainty.lower() != "none" and rpn.box_reg_loss_type == "smooth_l1" and rpn.smooth_l1_beta < 1e-5
+    """RPNWithIgnore.losses (rpn.py:129-204): the "IoUness" objectness of _dense_box_regression_loss_with_uncertainty
+    (rpn.py:206-273) or, with OBJECTNESS_UNCERTAINTY "none", the plain objectness and detectron2's _dense_box_regression_loss
+    (rpn.py:181-197).  logits (B,A), deltas (B,A,4); one fused kernel computes both sums, the logging counters and the gradients."""
     B, A = labels.shape
-    loss_conf, loss_loc, sums = ops.rpn_loss(logits, deltas, anchors, labels, midx, gt.boxes, rpn.box2box_transform.weights)
+    # the options are passed only when off their defaults: the CPU stand-in of this op (oracle/cpu_backend.py) states the default
+    # and has no such arguments, so it raises instead of computing the wrong loss
+    loss_conf, loss_loc, sums = ops.rpn_loss(logits, deltas, anchors, labels, midx, gt.boxes, rpn.box2box_transform.weights,
+                                             **rpn.loss_options())
     storage = get_event_storage()
     with torch.no_grad():
         # the four logging values as ONE vector expression: [npos, nneg, conf_pos, conf_neg] / [B, B, max(npos,1), max(rest,1)]
         cnt = sums[2:4] / B                                              # anchors per image: positive, negative
-        conf = sums[4:6] / torch.stack([sums[2], B * A - sums[2]]).clamp(min=1)
+        conf = None if rpn.objectness_none else sums[4:6] / torch.stack([sums[2], B * A - sums[2]]).clamp(min=1)
         storage.put_scalar("rpn/num_pos_anchors", cnt[0])
         storage.put_scalar("rpn/num_neg_anchors", cnt[1])
-        storage.put_scalar("rpn/conf_pos_anchors", conf[0])
-        storage.put_scalar("rpn/conf_neg_anchors", conf[1])
+        if conf is not None:                     # rpn.py:255-256 log these inside the IoU-weighted branch only
+            storage.put_scalar("rpn/conf_pos_anchors", conf[0])
+            storage.put_scalar("rpn/conf_neg_anchors", conf[1])
     normalizer = rpn.batch_size_per_image * B
     return {"rpn/cls": loss_conf * (rpn.loss_weight.get("rpn/cls", 1.0) / normalizer),
             "rpn/loc": loss_loc * (rpn.loss_weight.get("rpn/loc", 1.0) / normalizer)}
@@ -297,11 +301,11 @@ def box_head_losses(rh, features, samp, gt: GTBatch, pooled=None):
     if pooled is None:
         pooled = pool_roi_features(rh, features, samp)[0]
     box_features = rh.box_head(pooled)
-    scores, deltas = rh.box_predictor(box_features)                                    # (B*S,K+1), (B*S,K*4)
-    assert rh.box_predictor.smooth_l1_beta < 1e-5
+    scores, deltas = rh.box_predictor(box_features)                                    # (B*S,K+1), (B*S,K*4) or (B*S,4)
     t = rh.box_predictor.box2box_transform
+    # SMOOTH_L1_BETA > 0 / CLS_AGNOSTIC_BBOX_REG are passed only when set (see rpn_losses)
     sum_ce, sum_l1, sums, pred = ops.box_loss(scores, deltas, samp["valid"], samp["classes"], samp["boxes"], samp["gt_idx"],
-                                              gt.boxes, t.weights, t.scale_clamp)
+                                              gt.boxes, t.weights, t.scale_clamp, **rh.box_predictor.loss_options())
     inv = sums[2].clamp(min=1).reciprocal()
     lw = rh.box_predictor.loss_weight
     w_cls, w_reg = lw.get("BoxHead/loss_cls", 1.0), lw.get("BoxHead/loss_box_reg", 1.0)

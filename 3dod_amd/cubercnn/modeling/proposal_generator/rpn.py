@@ -13,6 +13,7 @@ import torch.nn.functional as F
 from ....d2lite import (PROPOSAL_GENERATOR_REGISTRY, RPN_HEAD_REGISTRY, Boxes, Instances, ShapeSpec, Box2BoxTransform,
                         Matcher, DefaultAnchorGenerator, cat, pairwise_iou, pairwise_ioa, get_event_storage)
 from .... import hipops as ops
+from ....hipops import rpn_reg_type_code          # option tables are no kernels: not part of what a CPU stand-in replaces
 from ..backbone.fpn import to_channels_last
 
 
@@ -250,6 +251,30 @@ class RPNWithIgnore(RPN):
         super().__init__(**kwargs)
         self.ignore_thresh = ignore_thresh
         self.objectness_uncertainty = objectness_uncertainty
+        # rpn.py:181-197 ("none": every detectron2 _dense_box_regression_loss type) / rpn.py:258-271 (any other value: smooth_l1
+        # only, the reference raises there): refused here, not inside the first training step
+        rpn_reg_type_code(self.box_reg_loss_type, self.objectness_none)
+        if not self.smooth_l1_beta >= 0:
+            raise ValueError(f"MODEL.RPN.SMOOTH_L1_BETA {self.smooth_l1_beta} < 0")
+
+    @property
+    def objectness_none(self):
+        """plain Faster R-CNN objectness (rpn.py:169: the test is `lower() in ['none']`; every other string is IoU-weighted)"""
+        return self.objectness_uncertainty.lower() == "none"
+
+    def loss_options(self):
+        """the ops.rpn_loss keywords of OBJECTNESS_UNCERTAINTY "none", BBOX_REG_LOSS_TYPE and SMOOTH_L1_BETA, each passed only when
+        it differs from its default: the CPU stand-in of this op (oracle/cpu_backend.py) states the default and has no such
+        arguments, so it raises instead of computing the wrong loss"""
+        opt = {}
+        if self.objectness_none:
+            opt["objectness_none"] = True
+        if self.box_reg_loss_type != "smooth_l1":
+            opt["box_reg_loss_type"] = self.box_reg_loss_type
+            opt["scale_clamp"] = self.box2box_transform.scale_clamp
+        elif not self.smooth_l1_beta < 1e-5:
+            opt["beta"] = float(self.smooth_l1_beta)
+        return opt
 
     @classmethod
     def from_config(cls, cfg, input_shape: Dict[str, ShapeSpec]):

@@ -136,9 +136,21 @@ class FastRCNNOutputLayers(nn.Module):
         self.test_nms_thresh = test_nms_thresh
         self.test_topk_per_image = test_topk_per_image
         self.box_reg_loss_type = box_reg_loss_type
+        self.cls_agnostic_bbox_reg = bool(cls_agnostic_bbox_reg)
         if isinstance(loss_weight, float):
             loss_weight = {"loss_cls": loss_weight, "loss_box_reg": loss_weight}
         self.loss_weight = loss_weight
+
+    def loss_options(self):
+        """the ops.box_loss keywords of SMOOTH_L1_BETA > 0 and CLS_AGNOSTIC_BBOX_REG, each passed only when it differs from its
+        default: the CPU stand-in of this op (oracle/cpu_backend.py) states the default and has no such arguments, so it raises
+        instead of computing the wrong loss"""
+        opt = {}
+        if not self.smooth_l1_beta < 1e-5:
+            opt["beta"] = float(self.smooth_l1_beta)
+        if self.cls_agnostic_bbox_reg:
+            opt["cls_agnostic"] = True
+        return opt
 
     def forward(self, x):
         if x.dim() > 2:
@@ -194,6 +206,15 @@ class FastRCNNOutputs(FastRCNNOutputLayers):
             box_reg_loss_type=cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE,
             loss_weight={"loss_box_reg": cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_WEIGHT},
         )
+        # losses() asks box_reg_loss for reduction="none" (fast_rcnn.py:186), whose only branch is smooth_l1: "giou" exists for
+        # reduction="mean" alone (fast_rcnn.py:223-227) and raises at fast_rcnn.py:254 in training.  Refused here, not inside the
+        # first training step
+        if self.box_reg_loss_type != "smooth_l1":
+            raise ValueError(f"Invalid bbox reg loss type '{self.box_reg_loss_type}' (fast_rcnn.py:254: FastRCNNOutputs.losses reduces "
+                             f"with 'none', for which the reference itself raises on anything but smooth_l1, 'giou' included; "
+                             f"built: ['smooth_l1'] with any SMOOTH_L1_BETA >= 0, class-specific or class-agnostic)")
+        if not self.smooth_l1_beta >= 0:
+            raise ValueError(f"MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA {self.smooth_l1_beta} < 0")
 
     def inference(self, predictions, proposals):
         boxes = self.predict_boxes(predictions, proposals)

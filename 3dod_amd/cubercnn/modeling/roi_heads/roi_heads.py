@@ -320,7 +320,10 @@ class ROIHeads3D(StandardROIHeads):
         survivors among them (ops.det_select's overflow flag): the caller then takes the per-image path."""
         import os
         bp = self.box_predictor
+        # (CLS_AGNOSTIC_BBOX_REG takes the per-image route, fast_rcnn_inference: ops.det_select accepts 4-wide deltas, but this route
+        # has no test with that option)
         if (os.environ.get("CR_INFER_FUSED", "1") == "0" or not proposals or getattr(self, "_forward_cube_list", None) is not None
+                or getattr(bp, "cls_agnostic_bbox_reg", False)
                 or not all(isinstance(p, Instances) and p.has("objectness_logits") for p in proposals)):
             return None
         B, P = len(proposals), len(proposals[0])

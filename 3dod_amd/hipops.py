@@ -17,6 +17,7 @@ in one process (the parity tests run them side by side).
 """
 import contextlib
 import ctypes
+import math
 import os
 
 import torch
@@ -1916,9 +1917,24 @@ def rpn_scatter(out, pos_idx, pos_key, neg_idx, neg_key, n_s, ioa, ignore_thresh
     return out
 
 
+# MODEL.RPN.BBOX_REG_LOSS_TYPE values cr_rpn_loss_opt computes (detectron2 _dense_box_regression_loss); the IoU family only with
+# OBJECTNESS_UNCERTAINTY "none" (rpn.py:271 raises for it on the IoU-weighted path)
+RPN_REG_TYPES = {"smooth_l1": 0, "giou": 1, "diou": 2, "ciou": 3}
+SCALE_CLAMP = math.log(1000.0 / 16)         # detectron2 Box2BoxTransform's default
+
+
+def rpn_reg_type_code(box_reg_loss_type, objectness_none):
+    """the reg_type code of cr_rpn_loss_opt, or the reference's ValueError (rpn.py:271 / detectron2 _dense_box_regression_loss)"""
+    built = sorted(RPN_REG_TYPES) if objectness_none else ["smooth_l1"]
+    if box_reg_loss_type not in built:
+        raise ValueError(f"Invalid dense box regression loss type '{box_reg_loss_type}' (rpn.py:271; built with "
+                         f"OBJECTNESS_UNCERTAINTY {'none' if objectness_none else 'other than none'}: {built})")
+    return RPN_REG_TYPES[box_reg_loss_type]
+
+
 class _RPNLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, deltas, anchors, labels, midx, gt_boxes, weights):
+    def forward(ctx, logits, deltas, anchors, labels, midx, gt_boxes, weights, opt=None):
         B, A = logits.shape
         G = gt_boxes.shape[1]
         dev = logits.device
@@ -1927,9 +1943,15 @@ class _RPNLoss(torch.autograd.Function):
         sums = torch.empty((6,), dtype=f32, device=dev)
         dl = torch.empty((B, A), dtype=f32, device=dev)
         dd = torch.empty((B, A, 4), dtype=f32, device=dev)
-        _lib.call("cr_rpn_loss", logits.detach().float().contiguous(), deltas.detach().float().contiguous(),
-                  anchors.contiguous(), labels.contiguous(), midx.contiguous(), gt_boxes.contiguous(), B, A, G, _f4(weights),
-                  ws, sums, dl, dd)
+        if opt is None:
+            _lib.call("cr_rpn_loss", logits.detach().float().contiguous(), deltas.detach().float().contiguous(),
+                      anchors.contiguous(), labels.contiguous(), midx.contiguous(), gt_boxes.contiguous(), B, A, G, _f4(weights),
+                      ws, sums, dl, dd)
+        else:
+            objectness, reg_type, beta, scale_clamp = opt
+            _lib.call("cr_rpn_loss_opt", logits.detach().float().contiguous(), deltas.detach().float().contiguous(),
+                      anchors.contiguous(), labels.contiguous(), midx.contiguous(), gt_boxes.contiguous(), B, A, G, _f4(weights),
+                      int(objectness), int(reg_type), float(beta), float(scale_clamp), ws, sums, dl, dd)
         ctx.save_for_backward(dl, dd)
         ctx.set_materialize_grads(False)       # outputs nobody differentiates arrive as None, not as zero fills
         ctx.mark_non_differentiable(sums)
@@ -1938,12 +1960,26 @@ class _RPNLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_cls, g_loc, _gs):
         dl, dd = ctx.saved_tensors
-        return (None if g_cls is None else dl * g_cls), (None if g_loc is None else dd * g_loc), None, None, None, None, None
+        return (None if g_cls is None else dl * g_cls), (None if g_loc is None else dd * g_loc), None, None, None, None, None, None
 
 
-def rpn_loss(logits, deltas, anchors, labels, midx, gt_boxes, weights):
-    """-> (loss_cls_sum, loss_loc_sum, sums6) unnormalised; labels (B,A) int32, midx (B,A) int32."""
+def rpn_loss(logits, deltas, anchors, labels, midx, gt_boxes, weights, **options):
+    """-> (loss_cls_sum, loss_loc_sum, sums6) unnormalised; labels (B,A) int32, midx (B,A) int32.  Without keywords: the default
+    options (IoU-weighted objectness, L1) on cr_rpn_loss; any keyword of rpn_loss_opt selects cr_rpn_loss_opt."""
+    if options:
+        return rpn_loss_opt(logits, deltas, anchors, labels, midx, gt_boxes, weights, **options)
     return _RPNLoss.apply(logits, deltas, anchors, labels, midx, gt_boxes, tuple(weights))
+
+
+def rpn_loss_opt(logits, deltas, anchors, labels, midx, gt_boxes, weights, objectness_none=False, box_reg_loss_type="smooth_l1",
+                 beta=0.0, scale_clamp=SCALE_CLAMP):
+    """rpn_loss for the other option sets (cr_rpn_loss_opt): objectness_none = OBJECTNESS_UNCERTAINTY "none" (rpn.py:181-197),
+    box_reg_loss_type smooth_l1 (with beta) / giou / diou / ciou, scale_clamp of the Box2BoxTransform for the IoU family."""
+    if not beta >= 0:
+        raise ValueError(f"smooth_l1 beta {beta} < 0")
+    code = rpn_reg_type_code(box_reg_loss_type, objectness_none)
+    return _RPNLoss.apply(logits, deltas, anchors, labels, midx, gt_boxes, tuple(weights),
+                          (1 if objectness_none else 0, code, float(beta), float(scale_clamp)))
 
 
 def roi_label(max_iou, argmax, max_ioa, valid, gt_classes, expo, K, thr, ignore_thresh, eps):
@@ -1974,20 +2010,30 @@ def roi_compact(fg_idx, fg_key, bg_idx, bg_key, n_s, boxes, cls, argmax):
 
 class _BoxLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, scores, deltas, valid, cls, pboxes, gt_idx, gt_boxes, weights, scale_clamp):
+    def forward(ctx, scores, deltas, valid, cls, pboxes, gt_idx, gt_boxes, weights, scale_clamp, opt=None):
         B, S = valid.shape
         N, C = scores.shape
         K = C - 1
         dev = scores.device
         nb = (N + 3) // 4
+        KD = 1 if opt is not None and opt[1] else K          # regression classes: one when class-agnostic
+        if N != B * S or tuple(deltas.shape) != (N, KD * 4):
+            raise ValueError(f"box_loss: scores {tuple(scores.shape)} / valid {tuple(valid.shape)} need deltas ({B * S}, {KD * 4}) "
+                             f"({'class-agnostic' if KD == 1 and K != 1 else 'class-specific'} regression), got {tuple(deltas.shape)}")
         ws = torch.empty((nb * 3,), dtype=f32, device=dev)
         sums = torch.empty((3,), dtype=f32, device=dev)
         ds = torch.empty((N, C), dtype=f32, device=dev)
-        dd = torch.empty((N, K * 4), dtype=f32, device=dev)
+        dd = torch.empty((N, KD * 4), dtype=f32, device=dev)
         pred = torch.empty((N, 4), dtype=f32, device=dev)
-        _lib.call("cr_box_loss", scores.detach().float().contiguous(), deltas.detach().float().contiguous(),
-                  valid.to(torch.uint8).contiguous(), cls.contiguous(), pboxes.contiguous(), gt_idx.contiguous(),
-                  gt_boxes.contiguous(), B, S, gt_boxes.shape[1], K, _f4(weights), float(scale_clamp), ws, sums, ds, dd, pred)
+        if opt is None:
+            _lib.call("cr_box_loss", scores.detach().float().contiguous(), deltas.detach().float().contiguous(),
+                      valid.to(torch.uint8).contiguous(), cls.contiguous(), pboxes.contiguous(), gt_idx.contiguous(),
+                      gt_boxes.contiguous(), B, S, gt_boxes.shape[1], K, _f4(weights), float(scale_clamp), ws, sums, ds, dd, pred)
+        else:
+            _lib.call("cr_box_loss_opt", scores.detach().float().contiguous(), deltas.detach().float().contiguous(),
+                      valid.to(torch.uint8).contiguous(), cls.contiguous(), pboxes.contiguous(), gt_idx.contiguous(),
+                      gt_boxes.contiguous(), B, S, gt_boxes.shape[1], K, _f4(weights), float(scale_clamp), float(opt[0]),
+                      1 if opt[1] else 0, ws, sums, ds, dd, pred)
         ctx.save_for_backward(ds, dd)
         ctx.dt = (scores.dtype, deltas.dtype)
         ctx.set_materialize_grads(False)       # outputs nobody differentiates arrive as None, not as zero fills
@@ -1998,12 +2044,24 @@ class _BoxLoss(torch.autograd.Function):
     def backward(ctx, g_ce, g_l1, _gs, _gp):
         ds, dd = ctx.saved_tensors
         return (None if g_ce is None else (ds * g_ce).to(ctx.dt[0])), (None if g_l1 is None else (dd * g_l1).to(ctx.dt[1])), \
-            None, None, None, None, None, None, None
+            None, None, None, None, None, None, None, None
 
 
-def box_loss(scores, deltas, valid, cls, pboxes, gt_idx, gt_boxes, weights, scale_clamp):
-    """-> (sum CE, sum L1, sums3 = [.., .., n_valid], pred (N,4)); valid/cls/gt_idx (B,S), pboxes (B,S,4)."""
+def box_loss(scores, deltas, valid, cls, pboxes, gt_idx, gt_boxes, weights, scale_clamp, **options):
+    """-> (sum CE, sum L1, sums3 = [.., .., n_valid], pred (N,4)); valid/cls/gt_idx (B,S), pboxes (B,S,4).  Without keywords: the
+    default options (L1, class-specific deltas (N,K*4)) on cr_box_loss; any keyword of box_loss_opt selects cr_box_loss_opt."""
+    if options:
+        return box_loss_opt(scores, deltas, valid, cls, pboxes, gt_idx, gt_boxes, weights, scale_clamp, **options)
     return _BoxLoss.apply(scores, deltas, valid, cls, pboxes, gt_idx, gt_boxes, tuple(weights), scale_clamp)
+
+
+def box_loss_opt(scores, deltas, valid, cls, pboxes, gt_idx, gt_boxes, weights, scale_clamp, beta=0.0, cls_agnostic=False):
+    """box_loss for the other option sets (cr_box_loss_opt): smooth_l1 beta (fast_rcnn.py:245-252) and class-agnostic regression
+    (deltas (N,4), fast_rcnn.py:207-208)."""
+    if not beta >= 0:
+        raise ValueError(f"smooth_l1 beta {beta} < 0")
+    return _BoxLoss.apply(scores, deltas, valid, cls, pboxes, gt_idx, gt_boxes, tuple(weights), scale_clamp,
+                          (float(beta), bool(cls_agnostic)))
 
 
 # --------------------------------------------------------------------------

@@ -540,6 +540,17 @@ int cr_rpn_scatter(cr_ctx* ctx, const int64_t* pos_idx, const float* pos_key, in
 int cr_rpn_loss(cr_ctx* ctx, const float* logits, const float* deltas, const float* anchors, const int* labels,
                 const int* matched_idx, const float* gt_boxes, int B, int A, int G, const float* weights4,
                 float* partial_ws, float* sums6, float* dlogits, float* ddeltas);
+/* cr_rpn_loss for the reference's other RPN loss options (same buffers, same sums6; the ABI version is unchanged):
+ * objectness 0 = any MODEL.RPN.OBJECTNESS_UNCERTAINTY but "none" (rpn.py:206-273: IoU target, both losses IoU-weighted),
+ *            1 = "none" (rpn.py:181-197: BCEWithLogits(logit, label) over label >= 0, localization over the positives, unweighted);
+ * reg_type 0 = smooth_l1 with `beta` (rpn.py:258-268; L1 when beta < 1e-5), 1 giou, 2 diou, 3 ciou of the box decoded with
+ *            Box2BoxTransform.apply_deltas(scale_clamp) -- detectron2 _dense_box_regression_loss and fvcore giou_loss / diou_loss /
+ *            ciou_loss (eps 1e-7, ciou's alpha held constant) [third-party, restated: parity unpinned]; 1-3 need objectness 1
+ *            (rpn.py:271 raises for them otherwise).  (0, 0, beta < 1e-5) launches cr_rpn_loss's own kernel. */
+int cr_rpn_loss_opt(cr_ctx* ctx, const float* logits, const float* deltas, const float* anchors, const int* labels,
+                    const int* matched_idx, const float* gt_boxes, int B, int A, int G, const float* weights4, int objectness,
+                    int reg_type, float beta, float scale_clamp, float* partial_ws, float* sums6, float* dlogits,
+                    float* ddeltas);
 
 /* ---- static-shape training glue of the RoI heads (3dod_amd/csrc/dense_train.hip) -------------------------------
  * cubercnn/modeling/roi_heads/roi_heads.py:2773-2840 (label_and_sample_proposals with ignore regions) and
@@ -562,6 +573,13 @@ int cr_box_loss(cr_ctx* ctx, const float* scores, const float* deltas, const uns
                 const float* prop_boxes, const int64_t* gt_idx, const float* gt_boxes, int B, int S, int G, int K,
                 const float* weights4, float scale_clamp, float* partial_ws, float* sums3, float* dscores, float* ddeltas,
                 float* pred);
+/* cr_box_loss for MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA > 0 (fast_rcnn.py:245-252: 0.5 e^2 / beta below beta, |e| - 0.5 beta above;
+ * L1 when beta < 1e-5) and CLS_AGNOSTIC_BBOX_REG (fast_rcnn.py:207-208: cls_agnostic != 0 -> deltas, ddeltas (B*S,4), every row
+ * regresses and decodes its one box).  (beta < 1e-5, 0) launches cr_box_loss's own kernel. */
+int cr_box_loss_opt(cr_ctx* ctx, const float* scores, const float* deltas, const unsigned char* valid, const int64_t* cls,
+                    const float* prop_boxes, const int64_t* gt_idx, const float* gt_boxes, int B, int S, int G, int K,
+                    const float* weights4, float scale_clamp, float beta, int cls_agnostic, float* partial_ws, float* sums3,
+                    float* dscores, float* ddeltas, float* pred);
 
 /* ---- glue around the fused 3D-head loss on the static-shape path (roi_heads.py:2237-2679, :2843-2851) ---------
  * raw (n, ld) f32 = fused predictor output, layout5 HOST = column offsets of [deltas 2K, dims 3K, pose6d 6K, z K,

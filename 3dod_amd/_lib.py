@@ -125,6 +125,15 @@ SIGNATURES = {
     "cr_transpose2d": [P, P, P, c_int, c_int, c_int],
     "cr_maxpool3x3s2_fwd": [P, P, P, c_int, c_int, c_int, c_int, c_int],
     "cr_maxpool3x3s2_bwd": [P, P, P, P, c_int, c_int, c_int, c_int, c_int],
+    "cr_dense_stats": [P, P, c_int64, c_int64, c_int, c_int, P, c_int, c_int, c_float, P, c_int],
+    "cr_dense_stats_finalize": [P, P, c_int, c_int, c_int64, P, c_int, c_int, c_float],
+    "cr_dense_slice_store": [P, P, P, c_int64, c_int64, c_int, c_int, c_int],
+    "cr_dense_slice_gather": [P, P, c_int64, c_int64, c_int, c_int, P, c_int],
+    "cr_dense_bn_fwd": [P, P, c_int64, c_int64, c_int, P, c_int, P, P, P, P, c_float, c_float, c_int, c_int, P, c_int],
+    "cr_dense_bn_bwd": [P, P, P, c_int64, c_int64, c_int, P, c_int, P, P, P, P, c_float, c_int, c_int, P, c_int64, c_int, P, P, P,
+                        c_int],
+    "cr_avgpool2x2_fwd": [P, P, P, c_int, c_int, c_int, c_int, c_int],
+    "cr_avgpool2x2_bwd": [P, P, P, c_int, c_int, c_int, c_int, c_int],
     "cr_cube_decode_infer": [P, P, c_int, P, c_int, P, P, P, P, P, c_int, c_int, P, c_int, c_int, P, P],
     "cr_cube_select_param": [P, P, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, c_int, c_int, P, P, P,
                              c_int, c_int, P, P],

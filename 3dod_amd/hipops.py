@@ -1295,6 +1295,215 @@ def subsample2x(x):
     return _Pool2x.apply(x, 1, _slot_register(x, True))
 
 
+# --------------------------------------------------------------------------
+# DenseNet (csrc/densenet.hip): a dense block as ONE autograd Function over a shared feature buffer, BatchNorm + ReLU on a
+# channel slice of it, average pooling.  None of these takes part in the gradient-slot protocol: a block output that also feeds
+# an FPN lateral gets its two gradients added by autograd.
+# --------------------------------------------------------------------------
+class _AvgPool2x2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        _need_cuda(x, "pool input")
+        N, H, W, C = x.shape
+        y = torch.empty((N, H // 2, W // 2, C), dtype=x.dtype, device=x.device)
+        _lib.call("cr_avgpool2x2_fwd", x.contiguous(), y, N, H, W, C, _af(x))
+        ctx.shape = (N, H, W, C)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        N, H, W, C = ctx.shape
+        dy = dy.contiguous()
+        dx = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
+        _lib.call("cr_avgpool2x2_bwd", dy, dx, N, H, W, C, _af(dy))
+        return dx
+
+
+def avgpool2x2(x):
+    """nn.AvgPool2d(kernel_size=2, stride=2) -- torchvision's DenseNet transitions; H and W must be even."""
+    return _AvgPool2x2.apply(x)
+
+
+def dense_stats(X, c0, C, tab, tab_off, eps):
+    """batch mean | biased variance | inverse std of the stored values X[..., c0 : c0 + C] -> tab[:, tab_off : tab_off + C]"""
+    ld = X.shape[-1]
+    ws = torch.empty((256 * 2 * C,), dtype=f32, device=X.device)
+    _lib.call("cr_dense_stats", X, X.numel() // ld, ld, c0, C, tab, tab.shape[1], tab_off, float(eps), ws, _af(X))
+
+
+def dense_slice_store(src, X, c0):
+    """X[..., c0 : c0 + C] = src (contiguous, C channels)"""
+    ld, C = X.shape[-1], src.shape[-1]
+    assert src.dtype == X.dtype and src.is_contiguous() and X.is_contiguous() and src.numel() // C == X.numel() // ld
+    _lib.call("cr_dense_slice_store", src, X, X.numel() // ld, ld, c0, C, _af(X))
+
+
+def dense_slice_gather(G, c0, C, dtype):
+    """G[..., c0 : c0 + C] of the float32 gradient buffer as a contiguous tensor of the activation dtype"""
+    assert G.dtype == f32 and G.is_contiguous()
+    ld = G.shape[-1]
+    out = torch.empty(tuple(G.shape[:-1]) + (C,), dtype=dtype, device=G.device)
+    _lib.call("cr_dense_slice_gather", G, G.numel() // ld, ld, c0, C, out, _af(out))
+    return out
+
+
+def dense_bn_fwd(X, C, tab, bn, gamma, beta, relu, batch):
+    """act(BatchNorm(X[..., :C])) contiguous; batch: statistics from tab and bn's running statistics updated, else bn's
+    running statistics.  gamma / beta: bn's weight / bias as the caller's autograd inputs"""
+    _need_cuda(X, "BatchNorm input")
+    ld = X.shape[-1]
+    out = torch.empty(tuple(X.shape[:-1]) + (C,), dtype=X.dtype, device=X.device)
+    _lib.call("cr_dense_bn_fwd", X, X.numel() // ld, ld, C, tab if batch else None, tab.shape[1] if batch else 0,
+              gamma.detach(), beta.detach(), bn.running_mean, bn.running_var, float(bn.eps), float(bn.momentum),
+              int(batch), int(relu), out, _af(X))
+    return out
+
+
+def dense_bn_bwd(da, X, C, tab, bn, gamma, beta, relu, batch, G, accumulate):
+    """adds (accumulate) or writes the gradient of dense_bn_fwd's input into G[..., :C]; -> (dgamma, dbeta), each None when
+    the parameter's gradient sink took it"""
+    gs, bs = grad_sink(gamma), grad_sink(beta)
+    if gs is not None and bs is not None:
+        dgamma, dbeta, ret_g, ret_b = gs, bs, None, None
+    else:
+        dgamma = torch.zeros((C,), dtype=f32, device=X.device)
+        dbeta = torch.zeros((C,), dtype=f32, device=X.device)
+        ret_g, ret_b = dgamma, dbeta
+    ld = X.shape[-1]
+    ws = torch.empty((257 * 2 * C,), dtype=f32, device=X.device)
+    _lib.call("cr_dense_bn_bwd", da, X, X.numel() // ld, ld, C, tab if batch else None, tab.shape[1] if batch else 0,
+              gamma.detach(), beta.detach(), bn.running_mean, bn.running_var, float(bn.eps), int(batch), int(relu), G,
+              G.shape[-1], int(accumulate), dgamma, dbeta, ws, _af(X))
+    return ret_g, ret_b
+
+
+class _DenseBlock(torch.autograd.Function):
+    """torchvision's _DenseBlock.  Per layer: slice BatchNorm + ReLU (cr_dense_bn_fwd) -> conv1 + norm2 + ReLU through
+    conv_bn_act, run as a small nested autograd graph (train, frozen and folded-eval forms are _ConvBN's / conv_bn_folded's own)
+    -> conv2 through conv_fwd_raw with statistics rows -> slice store + finalize.  The backward walks the layers in reverse over
+    ONE float32 gradient buffer: by the time layer i's 32 channels are gathered, every later layer has added into them."""
+    PER_LAYER = 6           # norm1.weight, norm1.bias, conv1.weight, norm2.weight, norm2.bias, conv2.weight
+
+    @staticmethod
+    def forward(ctx, x0, layers, *params):
+        _need_cuda(x0, "dense block input")
+        N, H, W, C0 = x0.shape
+        L, growth = len(layers), layers[0].conv2.weight.shape[0]
+        Ctot, M, dev = C0 + growth * L, N * H * W, x0.device
+        batch = bool(layers[0].norm1.training)
+        assert all(bool(l.norm1.training) == batch for l in layers), "a dense block's BatchNorms must share one mode"
+        grad = any(ctx.needs_input_grad)
+        X = torch.empty((N, H, W, Ctot), dtype=x0.dtype, device=dev)
+        dense_slice_store(x0.contiguous(), X, 0)
+        if batch:
+            _STATS_EPOCH[0] += 1
+            tab = torch.empty((3, Ctot), dtype=f32, device=dev)
+            dense_stats(X, 0, C0, tab, 0, layers[0].norm1.eps)
+            nparts = (M + 63) // 64
+        else:
+            tab = torch.zeros((3, Ctot), dtype=f32, device=dev)
+        saved = []
+        for i, layer in enumerate(layers):
+            C = C0 + growth * i
+            g1, b1, w1, g2, b2, w2 = params[6 * i:6 * i + 6]       # the autograd inputs: the backward asks for THESE tensors
+            n2 = layer.norm2
+            a = dense_bn_fwd(X, C, tab, layer.norm1, g1, b1, True, batch)
+            if grad:
+                a.requires_grad_(True)
+            with torch.set_grad_enabled(grad):
+                h = conv_bn_act(a, w1, g2, b2, n2.running_mean, n2.running_var, stride=1, pad=0, relu=True,
+                                eps=n2.eps, momentum=n2.momentum, training=n2.training)
+            wb, _ = prepared_weights(w2, grad, x0.dtype)
+            stats = torch.empty((nparts, 2, growth), dtype=f32, device=dev) if batch else None
+            y = conv_fwd_raw(h.detach(), wb, growth, 3, 1, 1, stats=stats)
+            dense_slice_store(y, X, C)
+            if batch:
+                _lib.call("cr_dense_stats_finalize", stats, nparts, growth, M, tab, Ctot, C, float(layer.norm1.eps))
+            if grad:
+                saved.append((a, h, g1, b1, w1, g2, b2, w2))
+        if grad:
+            ctx.layers, ctx.inner, ctx.cfg = layers, saved, (C0, growth, batch)
+            ctx.save_for_backward(X, tab)
+        ctx.mark_non_differentiable(tab)
+        return X, tab
+
+    @staticmethod
+    def backward(ctx, dX, _dtab):
+        X, tab = ctx.saved_tensors
+        layers, inner = ctx.layers, ctx.inner
+        C0, growth, batch = ctx.cfg
+        G = torch.empty(X.shape, dtype=f32, device=X.device)
+        G.copy_(dX)
+        grads = [None] * (_DenseBlock.PER_LAYER * len(layers))
+        for i in reversed(range(len(layers))):
+            layer, (a, h, g1, b1, w1, g2, b2, w2) = layers[i], inner[i]
+            inner[i] = None                                    # this layer's activations die with the iteration
+            C = C0 + growth * i
+            dy = dense_slice_gather(G, C, growth, X.dtype)
+            hd = h.detach()
+            _, wt = prepared_weights(w2, True, X.dtype)
+            dh = conv_bwd_data_raw(dy, wt, hd.shape, 3, 1, 1)
+            if ctx.needs_input_grad[2 + 6 * i + 5]:
+                grads[6 * i + 5] = conv_bwd_weight_raw(dy, hd, 3, 1, 1, grad_sink(w2))
+            wanted = [(k, t) for k, t in ((2, w1), (3, g2), (4, b2)) if ctx.needs_input_grad[2 + 6 * i + k]]
+            got = torch.autograd.grad([h], [a] + [t for _, t in wanted], [dh], allow_unused=True)
+            for (k, _), g in zip(wanted, got[1:]):
+                grads[6 * i + k] = g
+            da = got[0].to(X.dtype).contiguous()
+            dg, db = dense_bn_bwd(da, X, C, tab, layer.norm1, g1, b1, True, batch, G, True)
+            if ctx.needs_input_grad[2 + 6 * i]:
+                grads[6 * i] = dg
+            if ctx.needs_input_grad[2 + 6 * i + 1]:
+                grads[6 * i + 1] = db
+        dx0 = dense_slice_gather(G, 0, C0, X.dtype) if ctx.needs_input_grad[0] else None
+        ctx.inner = None
+        return (dx0, None) + tuple(grads)
+
+
+def dense_block(x0, layers):
+    """x0 (N,H,W,C0) -> (X (N,H,W,C0 + 32 L), tab (3, C0 + 32 L) f32, not differentiable).  layers: modules with norm1, conv1
+    (1x1), norm2, conv2 (3x3, pad 1) as parameter containers.  tab holds the batch statistics of every channel of X in train
+    mode (bn_act reuses it) and zeros in running-statistics mode."""
+    params = []
+    for l in layers:
+        params += [l.norm1.weight, l.norm1.bias, as_krsc(l.conv1.weight), l.norm2.weight, l.norm2.bias, as_krsc(l.conv2.weight)]
+    return _DenseBlock.apply(x0, tuple(layers), *params)
+
+
+class _BNAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, bn, relu, tab):
+        _need_cuda(x, "BatchNorm input")
+        C = x.shape[-1]
+        x = x.contiguous()
+        batch = bool(bn.training)
+        if batch:
+            _STATS_EPOCH[0] += 1
+            if tab is None:
+                tab = torch.empty((3, C), dtype=f32, device=x.device)
+                dense_stats(x, 0, C, tab, 0, bn.eps)
+        out = dense_bn_fwd(x, C, tab, bn, gamma, beta, relu, batch)
+        ctx.bn, ctx.cfg, ctx.affine = bn, (relu, batch), (gamma, beta)
+        ctx.save_for_backward(x, tab if batch else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, tab = ctx.saved_tensors
+        relu, batch = ctx.cfg
+        G = torch.empty(x.shape, dtype=f32, device=x.device)
+        dg, db = dense_bn_bwd(dout.to(x.dtype).contiguous(), x, x.shape[-1], tab, ctx.bn, *ctx.affine, relu, batch, G, False)
+        dx = G if x.dtype == f32 else dense_slice_gather(G, 0, x.shape[-1], x.dtype)
+        return (dx if ctx.needs_input_grad[0] else None, dg if ctx.needs_input_grad[1] else None,
+                db if ctx.needs_input_grad[2] else None, None, None, None)
+
+
+def bn_act(x, bn, relu, stats=None):
+    """BatchNorm2d (+ ReLU) of a whole NHWC map that no convolution precedes (DenseNet's transition norm and norm5): the slice
+    kernels at full width.  stats: the (3, C) table a dense_block returned for x, or None (computed here in train mode)."""
+    return _BNAct.apply(x, bn.weight, bn.bias, bn, relu, stats)
+
+
 class _UpsampleAdd(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lat, top, slot=(None, 0)):

@@ -477,6 +477,45 @@ int cr_cube_loss_bwd(cr_ctx* ctx, const float* const* inputs, int64_t n, int all
 int cr_maxpool3x3s2_fwd(cr_ctx* ctx, const void* x, void* y, int N, int H, int W, int C, int act_f32);
 int cr_maxpool3x3s2_bwd(cr_ctx* ctx, const void* x, const void* dy, void* dx, int N, int H, int W, int C, int act_f32);
 
+/* Dense blocks of the DenseNet-121 trunk (csrc/densenet.hip; cubercnn/modeling/backbone/densenet.py:10-38, which takes
+ * torchvision's densenet121.features [third-party]).  A block keeps one NHWC feature buffer x (M, ld), M = N*H*W, in the
+ * activation type (bf16, or f32 when act_f32 != 0; 1 and 2 are the same here): layer i reads channels [0, C_i) and its new
+ * channels are stored at [C_i, C_i + 32).  tab (3, ldt) f32 = batch mean | biased variance | 1 / sqrt(var + eps) per channel,
+ * written once per channel.  Channel counts C of the statistics / BatchNorm entry points: C % 32 == 0, 32 <= C <= 1024; ld and
+ * every channel offset are multiples of 8; anything else returns CR_EINVAL without a launch.  No atomics anywhere: reductions
+ * are a partial-sum launch plus a fixed-order finalize, bit-identical from run to run.
+ *   stats            sum / sum of squares of the STORED values x[:, c0 : c0 + C] -> tab[:, tab_off : tab_off + C];
+ *                    ws = 256 * 2 * C floats.
+ *   stats_finalize   the same table entries from the statistics rows cr_conv2d_fwd emitted (stats [nparts][2][C], M pixels).
+ *   slice_store      x[:, c0 : c0 + C] = src (M, C) contiguous, same type (C % 8 == 0).
+ *   slice_gather     dst (M, C) contiguous in the activation type = g[:, c0 : c0 + C] of the f32 gradient buffer g (M, ld).
+ *   bn_fwd           out (M, C) contiguous = relu?(gamma * (x[:, :C] - mean) * invstd + beta).  batch_stats != 0: mean / invstd
+ *                    from tab, and running_mean / running_var (may both be NULL) take momentum * (mean, unbiased variance);
+ *                    batch_stats == 0: mean = running_mean, invstd = 1 / sqrt(running_var + eps) (eval, freeze_bn).
+ *   bn_bwd           with the ReLU mask recomputed from x (as cr_bn_bwd_mask), g' = da * mask, xh = (x - mean) * invstd:
+ *                    dbeta += sum g', dgamma += sum g' xh (ACCUMULATED), and
+ *                    g[:, :C] (+)= gamma * invstd * (g' - sum g' / M - xh * sum(g' xh) / M)   (batch_stats != 0)
+ *                    g[:, :C] (+)= gamma * invstd * g'                                         (batch_stats == 0)
+ *                    g f32 (M, ldg) in every precision mode; accumulate != 0 adds, 0 overwrites; channels >= C untouched.
+ *                    ws = 257 * 2 * C floats. */
+int cr_dense_stats(cr_ctx* ctx, const void* x, int64_t M, int64_t ld, int c0, int C, float* tab, int ldt, int tab_off,
+                   float eps, float* ws, int act_f32);
+int cr_dense_stats_finalize(cr_ctx* ctx, const float* stats, int nparts, int C, int64_t M, float* tab, int ldt, int tab_off,
+                            float eps);
+int cr_dense_slice_store(cr_ctx* ctx, const void* src, void* x, int64_t M, int64_t ld, int c0, int C, int act_f32);
+int cr_dense_slice_gather(cr_ctx* ctx, const float* g, int64_t M, int64_t ld, int c0, int C, void* dst, int act_f32);
+int cr_dense_bn_fwd(cr_ctx* ctx, const void* x, int64_t M, int64_t ld, int C, const float* tab, int ldt, const float* gamma,
+                    const float* beta, float* running_mean, float* running_var, float eps, float momentum, int batch_stats,
+                    int relu, void* out, int act_f32);
+int cr_dense_bn_bwd(cr_ctx* ctx, const void* da, const void* x, int64_t M, int64_t ld, int C, const float* tab, int ldt,
+                    const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                    int batch_stats, int relu, float* g, int64_t ldg, int accumulate, float* dgamma, float* dbeta, float* ws,
+                    int act_f32);
+/* nn.AvgPool2d(kernel_size=2, stride=2) of torchvision's DenseNet transitions, NHWC; H, W even and C % 8 == 0, CR_EINVAL
+ * otherwise.  bwd: dx (N,H,W,C) = dy (N,H/2,W/2,C) / 4 spread over each window. */
+int cr_avgpool2x2_fwd(cr_ctx* ctx, const void* x, void* y, int N, int H, int W, int C, int act_f32);
+int cr_avgpool2x2_bwd(cr_ctx* ctx, const void* dy, void* dx, int N, int H, int W, int C, int act_f32);
+
 /* FC weights of the RoI heads (roi_heads.py:2160-2204, cube_head.py:152-202).  w f32 (O, C, HW) in the checkpoint's
  * (c,h,w) column order -> wb bf16 (O, HW, C) for NHWC-flattened inputs (HW = 1: plain cast); and the transpose for the
  * gradient: acc f32 (O, C, HW) += g bf16 (O, HW, C). */

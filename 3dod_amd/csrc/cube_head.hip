@@ -328,6 +328,64 @@ __device__ __forceinline__ void rot6d(const float* a, float* R, float* n1, float
     *n1 = l1; *nu = lu;
 }
 
+// dL/dR (9) -> dL/da through rot6d, whose R, l1, lu come in: out[0..2] to the first raw vector, out[3..5] to the second
+__device__ __forceinline__ void rot6d_bwd(const float* a, const float* R, float l1, float lu, const float* gR, float* out) {
+    const float* b1 = R; const float* b2 = R + 3;
+    // b3 = b1 x b2
+    float gb1[3] = {gR[0] + (b2[1] * gR[8] - b2[2] * gR[7]), gR[1] + (b2[2] * gR[6] - b2[0] * gR[8]),
+                    gR[2] + (b2[0] * gR[7] - b2[1] * gR[6])};
+    float gb2[3] = {gR[3] + (gR[7] * b1[2] - gR[8] * b1[1]), gR[4] + (gR[8] * b1[0] - gR[6] * b1[2]),
+                    gR[5] + (gR[6] * b1[1] - gR[7] * b1[0])};
+    // b2 = u / |u|
+    const float dot2 = gb2[0] * b2[0] + gb2[1] * b2[1] + gb2[2] * b2[2];
+    float gu[3] = {(gb2[0] - dot2 * b2[0]) / lu, (gb2[1] - dot2 * b2[1]) / lu, (gb2[2] - dot2 * b2[2]) / lu};
+    // u = a2 - d b1, d = b1 . a2
+    const float d = b1[0] * a[3] + b1[1] * a[4] + b1[2] * a[5];
+    const float gd = -(gu[0] * b1[0] + gu[1] * b1[1] + gu[2] * b1[2]);
+    float ga2[3] = {gu[0] + gd * b1[0], gu[1] + gd * b1[1], gu[2] + gd * b1[2]};
+    for (int k = 0; k < 3; ++k) gb1[k] += -d * gu[k] + gd * a[3 + k];
+    // b1 = a1 / |a1|
+    const float dot1 = gb1[0] * b1[0] + gb1[1] * b1[1] + gb1[2] * b1[2];
+    for (int k = 0; k < 3; ++k) { out[k] = (gb1[k] - dot1 * b1[k]) / l1; out[3 + k] = ga2[k]; }
+}
+
+// what a forward selection copies without arithmetic: the camera constants of image b and the ground truth matched to RoI i
+// (slot gi of the image, sanitised where the RoI is not valid) -> the K4, v2r, gt2d, gtz, gtdims and gtR chunks of buf39
+__device__ __forceinline__ void select_meta_gt(const CubeSel& p, int b, int i, int64_t gi, bool v, float* o) {
+    const size_t n = p.n;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[CUBE_OFF[5] * n + i * 4 + k] = p.meta[b * 5 + k];
+    o[CUBE_OFF[6] * n + i] = p.meta[b * 5 + 4];
+    const float* g3 = p.gt3d + ((size_t)b * p.G + gi) * 9;
+    const float safe[6] = {256.f, 256.f, 5.f, 1.f, 1.f, 1.f};      // a unit cube 5 m in front of the camera
+    o[CUBE_OFF[8] * n + i * 2] = v ? g3[0] : safe[0]; o[CUBE_OFF[8] * n + i * 2 + 1] = v ? g3[1] : safe[1];
+    o[CUBE_OFF[9] * n + i] = v ? g3[2] : safe[2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[CUBE_OFF[10] * n + i * 3 + k] = v ? g3[3 + k] : safe[3 + k];
+    const float* gp = p.gtpose + ((size_t)b * p.G + gi) * 9;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) o[CUBE_OFF[11] * n + i * 9 + k] = gp[k];
+}
+
+#define CUBE_POSE_W_MAX 6                                   // widest pose block per class ('6d')
+#define CUBE_SEL_STAGE (2 + 3 + CUBE_POSE_W_MAX + 1 + 1)    // staged per RoI by a backward selection: dxy, dims, pose, z, u
+
+// the wave writes the dense gradient row g of a RoI with class c: the staged s = [dxy 2 | dims 3 | pose | z | u] at the class's
+// columns (pw pose columns, depth column zcol, the uncertainty column only with `unc`), zeros everywhere else
+__device__ __forceinline__ void select_scatter_row(const CubeSel& p, int c, int zcol, int pw, bool unc, const float* s, float* g,
+                                                   int lane) {
+    for (int col = lane; col < p.ld; col += 64) {
+        float val = 0.f;
+        int e;
+        if ((e = col - (p.o_d2 + c * 2)) >= 0 && e < 2) val = s[e];
+        else if ((e = col - (p.o_dims + c * 3)) >= 0 && e < 3) val = s[2 + e];
+        else if ((e = col - (p.o_pose + c * pw)) >= 0 && e < pw) val = s[5 + e];
+        else if (col == zcol) val = s[CUBE_SEL_STAGE - 2];
+        else if (unc && col == p.o_unc + c) val = s[CUBE_SEL_STAGE - 1];
+        g[col] = val;
+    }
+}
+
 __global__ __launch_bounds__(64) void k_cube_select(CubeSel p, float* __restrict__ buf, unsigned char* __restrict__ validf,
                                                     int* __restrict__ clsc) {
     const int i = blockIdx.x * 64 + threadIdx.x;
@@ -354,20 +412,8 @@ __global__ __launch_bounds__(64) void k_cube_select(CubeSel p, float* __restrict
     for (int k = 0; k < 9; ++k) o[CUBE_OFF[3] * n + i * 9 + k] = R[k];
     o[CUBE_OFF[4] * n + i] = fmaxf(r[p.o_unc + c], 0.01f);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) o[CUBE_OFF[5] * n + i * 4 + k] = p.meta[b * 5 + k];
-    o[CUBE_OFF[6] * n + i] = p.meta[b * 5 + 4];
-#pragma unroll
     for (int k = 0; k < 3; ++k) o[CUBE_OFF[7] * n + i * 3 + k] = p.priors ? p.priors[c * 3 + k] : 1.f;
-    const int64_t gi = p.gt_idx[bs];
-    const float* g3 = p.gt3d + ((size_t)b * p.G + gi) * 9;
-    const float safe[6] = {256.f, 256.f, 5.f, 1.f, 1.f, 1.f};      // a unit cube 5 m in front of the camera
-    o[CUBE_OFF[8] * n + i * 2] = v ? g3[0] : safe[0]; o[CUBE_OFF[8] * n + i * 2 + 1] = v ? g3[1] : safe[1];
-    o[CUBE_OFF[9] * n + i] = v ? g3[2] : safe[2];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o[CUBE_OFF[10] * n + i * 3 + k] = v ? g3[3 + k] : safe[3 + k];
-    const float* gp = p.gtpose + ((size_t)b * p.G + gi) * 9;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) o[CUBE_OFF[11] * n + i * 9 + k] = gp[k];
+    select_meta_gt(p, b, i, p.gt_idx[bs], v, o);
 }
 
 // one wave per RoI: lane 0 back-propagates to the 13 selected predictor outputs, the wave writes the dense row
@@ -376,70 +422,60 @@ __global__ __launch_bounds__(64) void k_cube_select_bwd(CubeSel p, const unsigne
                                                         const float* __restrict__ g_zr, const float* __restrict__ g_dr,
                                                         const float* __restrict__ g_Ra, const float* __restrict__ g_u,
                                                         const float* __restrict__ g_usel, float* __restrict__ g_raw) {
-    __shared__ float s[13];
+    __shared__ float s[CUBE_SEL_STAGE];
     const int i = blockIdx.x, lane = threadIdx.x;
     const int c = clsc[i];
     const bool v = validf[i] != 0;
     const float* r = p.raw + (size_t)i * p.ld;
     if (lane == 0) {
         if (!v) {
-            for (int k = 0; k < 13; ++k) s[k] = 0.f;
+            for (int k = 0; k < CUBE_SEL_STAGE; ++k) s[k] = 0.f;
         } else {
             s[0] = g_dxy[i * 2]; s[1] = g_dxy[i * 2 + 1];
             s[2] = g_dr[i * 3]; s[3] = g_dr[i * 3 + 1]; s[4] = g_dr[i * 3 + 2];
             float a[6], R[9], l1, lu;
             for (int k = 0; k < 6; ++k) a[k] = r[p.o_pose + c * 6 + k];
             rot6d(a, R, &l1, &lu);
-            const float* gR = g_Ra + (size_t)i * 9;
-            const float* b1 = R; const float* b2 = R + 3;
-            // b3 = b1 x b2
-            float gb1[3] = {gR[0] + (b2[1] * gR[8] - b2[2] * gR[7]), gR[1] + (b2[2] * gR[6] - b2[0] * gR[8]),
-                            gR[2] + (b2[0] * gR[7] - b2[1] * gR[6])};
-            float gb2[3] = {gR[3] + (gR[7] * b1[2] - gR[8] * b1[1]), gR[4] + (gR[8] * b1[0] - gR[6] * b1[2]),
-                            gR[5] + (gR[6] * b1[1] - gR[7] * b1[0])};
-            // b2 = u / |u|
-            const float dot2 = gb2[0] * b2[0] + gb2[1] * b2[1] + gb2[2] * b2[2];
-            float gu[3] = {(gb2[0] - dot2 * b2[0]) / lu, (gb2[1] - dot2 * b2[1]) / lu, (gb2[2] - dot2 * b2[2]) / lu};
-            // u = a2 - d b1, d = b1 . a2
-            const float d = b1[0] * a[3] + b1[1] * a[4] + b1[2] * a[5];
-            const float gd = -(gu[0] * b1[0] + gu[1] * b1[1] + gu[2] * b1[2]);
-            float ga2[3] = {gu[0] + gd * b1[0], gu[1] + gd * b1[1], gu[2] + gd * b1[2]};
-            for (int k = 0; k < 3; ++k) gb1[k] += -d * gu[k] + gd * a[3 + k];
-            // b1 = a1 / |a1|
-            const float dot1 = gb1[0] * b1[0] + gb1[1] * b1[1] + gb1[2] * b1[2];
-            for (int k = 0; k < 3; ++k) { s[5 + k] = (gb1[k] - dot1 * b1[k]) / l1; s[8 + k] = ga2[k]; }
+            rot6d_bwd(a, R, l1, lu, g_Ra + (size_t)i * 9, s + 5);
             { float dz; z_of(r, p.o_z, p.K, c, i, p.z_type, p.bins, p.z_scales, p.z_stats, p.boxes, &dz, nullptr); s[11] = g_zr[i] * dz; }
             s[12] = r[p.o_unc + c] >= 0.01f ? g_u[i] + g_usel[i] : 0.f;      // clip(0.01) passes the gradient where raw >= 0.01
         }
     }
     __syncthreads();
     const int zcol = p.o_z + z_bin(p.z_scales, p.boxes, p.bins, i, c) * p.K + c;
-    float* g = g_raw + (size_t)i * p.ld;
-    for (int col = lane; col < p.ld; col += 64) {
-        float val = 0.f;
-        int e;
-        if ((e = col - (p.o_d2 + c * 2)) >= 0 && e < 2) val = s[e];
-        else if ((e = col - (p.o_dims + c * 3)) >= 0 && e < 3) val = s[2 + e];
-        else if ((e = col - (p.o_pose + c * 6)) >= 0 && e < 6) val = s[5 + e];
-        else if (col == zcol) val = s[11];
-        else if (col == p.o_unc + c) val = s[12];
-        g[col] = val;
-    }
+    select_scatter_row(p, c, zcol, 6, true, s, g_raw + (size_t)i * p.ld, lane);
 }
 
-static int cube_sel_args(CubeSel& p, const float* raw, int ld, const int* layout5, int K, const int64_t* cls,
-                         const unsigned char* valid, const int64_t* gt_idx, int B, int S, int kf, int G, const float* gt3d,
-                         const float* gtpose, const float* priors, const float* meta, int z_type, int bins,
-                         const float* z_scales, const float* z_stats, const float* boxes) {
-    CR_CHECK_ARG(raw && layout5 && cls && valid && gt_idx && gt3d && gtpose && meta, "cube_select: NULL pointer");
-    CR_CHECK_ARG(bins >= 1 && B > 0 && kf > 0 && kf <= S && G > 0 && K > 0 && ld >= (12 + bins) * K, "cube_select: bad sizes");
-    CR_CHECK_ARG(bins == 1 || (z_scales && boxes), "cube_select: CLUSTER_BINS > 1 needs the scale centres and the RoI boxes");
-    CR_CHECK_ARG(z_type != 3 || (bins > 1 && z_stats), "cube_select: Z_TYPE 'clusters' needs CLUSTER_BINS > 1 and the depth statistics");
+// The one filler and validator of CubeSel, for every selection and decode entry point of both families: the raw rows, the
+// depth parametrisation and the predictor layout against the row stride -- every block [offset, offset + width * K) lies inside
+// a row of ld columns.  pw: pose columns per class.  The default family always reads an uncertainty block (need_unc); without
+// one the parametrised family passes a negative offset.  kf, n and the per-RoI inputs of a forward selection are the caller's
+// (cube_sel_inputs).
+static int cube_sel_fill(CubeSel& p, const char* who, const float* raw, int ld, const int* layout5, int K, int pw, bool need_unc,
+                         int z_type, int bins, const float* z_scales, const float* z_stats, const float* boxes) {
+    CR_CHECK_ARG(raw && layout5 && K > 0 && bins >= 1 && ld > 0, "%s: bad sizes", who);
+    CR_CHECK_ARG(z_type >= 0 && z_type <= 3, "%s: z_type %d (0 direct, 1 sigmoid, 2 log, 3 clusters)", who, z_type);
+    CR_CHECK_ARG(bins == 1 || (z_scales && boxes), "%s: CLUSTER_BINS > 1 needs the scale centres and the RoI boxes", who);
+    CR_CHECK_ARG(z_type != 3 || (bins > 1 && z_stats), "%s: Z_TYPE 'clusters' needs CLUSTER_BINS > 1 and the depth statistics", who);
+    const int64_t K64 = K;
+    CR_CHECK_ARG(layout5[0] >= 0 && layout5[0] + 2 * K64 <= ld && layout5[1] >= 0 && layout5[1] + 3 * K64 <= ld &&
+                     layout5[2] >= 0 && layout5[2] + pw * K64 <= ld && layout5[3] >= 0 && layout5[3] + bins * K64 <= ld &&
+                     (layout5[4] < 0 ? !need_unc : layout5[4] + K64 <= ld),
+                 "%s: the predictor layout does not fit a row of %d columns", who, ld);
+    p = CubeSel{};
     p.raw = raw; p.ld = ld; p.o_d2 = layout5[0]; p.o_dims = layout5[1]; p.o_pose = layout5[2]; p.o_z = layout5[3];
-    p.o_unc = layout5[4]; p.K = K; p.cls = cls; p.valid = valid; p.gt_idx = gt_idx; p.S = S; p.kf = kf; p.G = G; p.n = B * kf;
-    p.gt3d = gt3d; p.gtpose = gtpose; p.priors = priors; p.meta = meta; p.z_type = z_type;
-    p.bins = bins; p.z_scales = z_scales; p.z_stats = z_stats; p.boxes = boxes;
-    CR_CHECK_ARG(z_type >= 0 && z_type <= 3, "cube_select: z_type %d (0 direct, 1 sigmoid, 2 log, 3 clusters)", z_type);
+    p.o_unc = layout5[4] < 0 ? -1 : layout5[4]; p.K = K; p.z_type = z_type; p.bins = bins;
+    p.z_scales = z_scales; p.z_stats = z_stats; p.boxes = boxes;
+    return CR_OK;
+}
+
+// what only a forward selection reads: the sampled classes, the matched ground truth, the camera constants and the priors
+static int cube_sel_inputs(CubeSel& p, const char* who, const int64_t* cls, const unsigned char* valid, const int64_t* gt_idx, int B,
+                           int S, int kf, int G, const float* gt3d, const float* gtpose, const float* priors, const float* meta) {
+    CR_CHECK_ARG(cls && valid && gt_idx && gt3d && gtpose && meta, "%s: NULL pointer", who);
+    CR_CHECK_ARG(B > 0 && kf > 0 && kf <= S && G > 0, "%s: bad sizes", who);
+    p.cls = cls; p.valid = valid; p.gt_idx = gt_idx; p.S = S; p.kf = kf; p.G = G; p.n = B * kf;
+    p.gt3d = gt3d; p.gtpose = gtpose; p.priors = priors; p.meta = meta;
     return CR_OK;
 }
 
@@ -450,8 +486,8 @@ extern "C" int cr_cube_select(cr_ctx* ctx, const float* raw, int ld, const int* 
                               const float* z_stats, const float* boxes) {
     CR_CHECK_ARG(ctx && buf39 && validf && clsc, "cr_cube_select: NULL pointer");
     CubeSel p;
-    int rc = cube_sel_args(p, raw, ld, layout5, K, cls, valid, gt_idx, B, S, kf, G, gt3d, gtpose, priors, meta, z_type, bins, z_scales,
-                           z_stats, boxes);
+    int rc = cube_sel_fill(p, "cr_cube_select", raw, ld, layout5, K, 6, true, z_type, bins, z_scales, z_stats, boxes);
+    if (!rc) rc = cube_sel_inputs(p, "cr_cube_select", cls, valid, gt_idx, B, S, kf, G, gt3d, gtpose, priors, meta);
     if (rc) return rc;
     hipLaunchKernelGGL(k_cube_select, dim3((unsigned)cr_cdiv(p.n, 64)), dim3(64), 0, ctx->stream, p, buf39, validf, clsc);
     CR_LAUNCH_CHECK();
@@ -462,14 +498,12 @@ extern "C" int cr_cube_select_bwd(cr_ctx* ctx, const float* raw, int ld, const i
                                   const unsigned char* validf, const int* clsc, const float* g_dxy, const float* g_zr,
                                   const float* g_dr, const float* g_Ra, const float* g_u, const float* g_usel, float* g_raw,
                                   int z_type, int bins, const float* z_scales, const float* z_stats, const float* boxes) {
-    CR_CHECK_ARG(ctx && raw && layout5 && validf && clsc && g_dxy && g_zr && g_dr && g_Ra && g_u && g_usel && g_raw,
+    CR_CHECK_ARG(ctx && validf && clsc && g_dxy && g_zr && g_dr && g_Ra && g_u && g_usel && g_raw && B >= 0 && kf >= 0,
                  "cr_cube_select_bwd: NULL pointer");
-    CR_CHECK_ARG(z_type >= 0 && z_type <= 3 && bins >= 1 && (bins == 1 || (z_scales && boxes)) && (z_type != 3 || z_stats),
-                 "cr_cube_select_bwd: z_type %d / bins %d", z_type, bins);
-    CubeSel p = {};
-    p.z_type = z_type; p.bins = bins; p.z_scales = z_scales; p.z_stats = z_stats; p.boxes = boxes;
-    p.raw = raw; p.ld = ld; p.o_d2 = layout5[0]; p.o_dims = layout5[1]; p.o_pose = layout5[2]; p.o_z = layout5[3];
-    p.o_unc = layout5[4]; p.K = K; p.kf = kf; p.n = B * kf;
+    CubeSel p;
+    int rc = cube_sel_fill(p, "cr_cube_select_bwd", raw, ld, layout5, K, 6, true, z_type, bins, z_scales, z_stats, boxes);
+    if (rc) return rc;
+    p.kf = kf; p.n = B * kf;
     if (p.n == 0) return CR_OK;
     hipLaunchKernelGGL(k_cube_select_bwd, dim3(p.n), dim3(64), 0, ctx->stream, p, validf, clsc, g_dxy, g_zr, g_dr, g_Ra, g_u,
                        g_usel, g_raw);
@@ -668,24 +702,14 @@ __global__ __launch_bounds__(64) void k_cube_select_bwd_zraw(CubeSel p, const un
     g_raw[(size_t)i * p.ld + p.o_z + z_bin(p.z_scales, p.boxes, p.bins, i, c) * p.K + c] += g_zraw[i];
 }
 
-static int cube_norm_args(CubeSel& p, const float* raw, int ld, const int* layout5, int K, int B, int kf, int z_type, int bins,
-                          const float* z_scales, const float* z_stats, const float* boxes) {
-    CR_CHECK_ARG(raw && layout5 && B > 0 && kf > 0 && K > 0 && bins >= 1 && ld >= (12 + bins) * K, "cube_select_norm: bad sizes");
-    CR_CHECK_ARG(z_type >= 0 && z_type <= 3 && (bins == 1 || (z_scales && boxes)) && (z_type != 3 || (bins > 1 && z_stats)),
-                 "cube_select_norm: z_type %d / bins %d", z_type, bins);
-    p = CubeSel{};
-    p.raw = raw; p.ld = ld; p.o_z = layout5[3]; p.K = K; p.kf = kf; p.n = B * kf;
-    p.z_type = z_type; p.bins = bins; p.z_scales = z_scales; p.z_stats = z_stats; p.boxes = boxes;
-    return CR_OK;
-}
-
 extern "C" int cr_cube_select_norm(cr_ctx* ctx, const float* raw, int ld, const int* layout5, int K, int B, int kf,
                                    const int* clsc, int z_type, int bins, const float* z_scales, const float* z_stats,
                                    const float* boxes, float* norm3) {
-    CR_CHECK_ARG(ctx && clsc && norm3, "cr_cube_select_norm: NULL pointer");
+    CR_CHECK_ARG(ctx && clsc && norm3 && B > 0 && kf > 0, "cr_cube_select_norm: bad args");
     CubeSel p;
-    int rc = cube_norm_args(p, raw, ld, layout5, K, B, kf, z_type, bins, z_scales, z_stats, boxes);
+    int rc = cube_sel_fill(p, "cr_cube_select_norm", raw, ld, layout5, K, 6, true, z_type, bins, z_scales, z_stats, boxes);
     if (rc) return rc;
+    p.kf = kf; p.n = B * kf;
     hipLaunchKernelGGL(k_cube_select_norm, dim3((unsigned)cr_cdiv(p.n, 64)), dim3(64), 0, ctx->stream, p, clsc, norm3);
     CR_LAUNCH_CHECK();
     return CR_OK;
@@ -694,10 +718,11 @@ extern "C" int cr_cube_select_norm(cr_ctx* ctx, const float* raw, int ld, const 
 extern "C" int cr_cube_select_bwd_zraw(cr_ctx* ctx, int ld, const int* layout5, int K, int B, int kf,
                                        const unsigned char* validf, const int* clsc, const float* g_zraw, float* g_raw,
                                        int bins, const float* z_scales, const float* boxes) {
-    CR_CHECK_ARG(ctx && validf && clsc && g_zraw && g_raw, "cr_cube_select_bwd_zraw: NULL pointer");
+    CR_CHECK_ARG(ctx && validf && clsc && g_zraw && g_raw && B > 0 && kf > 0, "cr_cube_select_bwd_zraw: bad args");
     CubeSel p;
-    int rc = cube_norm_args(p, g_raw, ld, layout5, K, B, kf, 0, bins, z_scales, nullptr, boxes);
+    int rc = cube_sel_fill(p, "cr_cube_select_bwd_zraw", g_raw, ld, layout5, K, 6, true, 0, bins, z_scales, nullptr, boxes);
     if (rc) return rc;
+    p.kf = kf; p.n = B * kf;
     hipLaunchKernelGGL(k_cube_select_bwd_zraw, dim3((unsigned)cr_cdiv(p.n, 64)), dim3(64), 0, ctx->stream, p, validf, clsc,
                        g_zraw, g_raw);
     CR_LAUNCH_CHECK();
@@ -877,12 +902,15 @@ extern "C" int cr_cube_decode_infer(cr_ctx* ctx, const float* raw, int ld, const
                                     const int* img, const float* boxes, const float* meta6, const float* priors, int n,
                                     int allocentric, float* out42, int z_type, int bins, const float* z_scales,
                                     const float* z_stats) {
-    CR_CHECK_ARG(ctx && n >= 0 && z_type >= 0 && z_type <= 3 && bins >= 1, "cr_cube_decode_infer: bad args");
-    CR_CHECK_ARG((bins == 1 || z_scales) && (z_type != 3 || (bins > 1 && z_stats)), "cr_cube_decode_infer: cluster tables missing");
+    CR_CHECK_ARG(ctx && n >= 0, "cr_cube_decode_infer: bad args");
     if (n == 0) return CR_OK;
-    CR_CHECK_ARG(raw && layout5 && cls && img && boxes && meta6 && out42 && K > 0 && ld >= (12 + bins) * K, "cr_cube_decode_infer: bad args");
-    hipLaunchKernelGGL(k_cube_decode_infer, dim3((unsigned)cr_cdiv(n, 64)), dim3(64), 0, ctx->stream, raw, ld, layout5[0],
-                       layout5[1], layout5[2], layout5[3], layout5[4], K, cls, img, boxes, meta6, priors, n, allocentric, out42, z_type, bins, z_scales, z_stats);
+    CR_CHECK_ARG(cls && img && boxes && meta6 && out42, "cr_cube_decode_infer: NULL pointer");
+    CubeSel p;
+    int rc = cube_sel_fill(p, "cr_cube_decode_infer", raw, ld, layout5, K, 6, true, z_type, bins, z_scales, z_stats, boxes);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_cube_decode_infer, dim3((unsigned)cr_cdiv(n, 64)), dim3(64), 0, ctx->stream, raw, ld, p.o_d2, p.o_dims,
+                       p.o_pose, p.o_z, p.o_unc, K, cls, img, boxes, meta6, priors, n, allocentric, out42, z_type, bins, z_scales,
+                       z_stats);
     CR_LAUNCH_CHECK();
     return CR_OK;
 }
@@ -911,9 +939,6 @@ extern "C" int cr_cube_decode_infer(cr_ctx* ctx, const float* raw, int ld, const
 // cube_3D[:, -1]; without the confidence column the last column is the y coordinate of the projected 2D centre times the image
 // ratio (column 7).  A quirk of the reference, reproduced.
 // ---------------------------------------------------------------------------------------------------------------
-#define CUBE_POSE_W_MAX 6                                   // widest pose block per class ('6d')
-#define CUBE_SEL_STAGE (2 + 3 + CUBE_POSE_W_MAX + 1 + 1)    // staged per RoI by the backward selection: dxy, dims, pose, z, u
-
 struct CubeSelP {
     CubeSel s;
     int pose_type, dims_func;
@@ -1043,20 +1068,8 @@ __global__ __launch_bounds__(64) void k_cube_select_param(CubeSelP pp, float* __
 #pragma unroll
     for (int k = 0; k < 9; ++k) o[CUBE_OFF[3] * n + i * 9 + k] = R[k];
     o[CUBE_OFF[4] * n + i] = p.o_unc >= 0 ? fmaxf(r[p.o_unc + c], 0.01f) : 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[CUBE_OFF[5] * n + i * 4 + k] = p.meta[b * 5 + k];
-    o[CUBE_OFF[6] * n + i] = p.meta[b * 5 + 4];
-    int64_t gi = p.gt_idx[bs];
-    gi = gi < 0 ? 0 : (gi >= p.G ? p.G - 1 : gi);
-    const float* g3 = p.gt3d + ((size_t)b * p.G + gi) * 9;
-    const float safe[6] = {256.f, 256.f, 5.f, 1.f, 1.f, 1.f};      // a unit cube 5 m in front of the camera
-    o[CUBE_OFF[8] * n + i * 2] = v ? g3[0] : safe[0]; o[CUBE_OFF[8] * n + i * 2 + 1] = v ? g3[1] : safe[1];
-    o[CUBE_OFF[9] * n + i] = v ? g3[2] : safe[2];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o[CUBE_OFF[10] * n + i * 3 + k] = v ? g3[3 + k] : safe[3 + k];
-    const float* gp = p.gtpose + ((size_t)b * p.G + gi) * 9;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) o[CUBE_OFF[11] * n + i * 9 + k] = gp[k];
+    const int64_t gi = p.gt_idx[bs];
+    select_meta_gt(p, b, i, gi < 0 ? 0 : (gi >= p.G ? p.G - 1 : gi), v, o);
 }
 
 // one wave per RoI, as k_cube_select_bwd: lane 0 back-propagates to the selected predictor outputs -- staged as
@@ -1108,32 +1121,11 @@ __global__ __launch_bounds__(64) void k_cube_select_param_bwd(CubeSelP pp, const
 #pragma unroll
                 for (int k = 0; k < 3; ++k) s[5 + k] = ge[k];
             } else {
-                // the Gram-Schmidt backward of k_cube_select_bwd, whose device code is pinned and therefore not shared: a change
-                // to either copy goes into both.  No test compares the two copies' gradients to each other; tests/test_gpu_cube_params.py
-                // holds each to the float64 definition at 4 x the float32 floor and compares their zero patterns and copied chunks
                 float a[6], R[9], l1, lu;
 #pragma unroll
                 for (int k = 0; k < 6; ++k) a[k] = r[p.o_pose + c * 6 + k];
                 rot6d(a, R, &l1, &lu);
-                const float* b1 = R; const float* b2 = R + 3;
-                // b3 = b1 x b2
-                float gb1[3] = {gR[0] + (b2[1] * gR[8] - b2[2] * gR[7]), gR[1] + (b2[2] * gR[6] - b2[0] * gR[8]),
-                                gR[2] + (b2[0] * gR[7] - b2[1] * gR[6])};
-                float gb2[3] = {gR[3] + (gR[7] * b1[2] - gR[8] * b1[1]), gR[4] + (gR[8] * b1[0] - gR[6] * b1[2]),
-                                gR[5] + (gR[6] * b1[1] - gR[7] * b1[0])};
-                // b2 = u / |u|
-                const float dot2 = gb2[0] * b2[0] + gb2[1] * b2[1] + gb2[2] * b2[2];
-                float gu[3] = {(gb2[0] - dot2 * b2[0]) / lu, (gb2[1] - dot2 * b2[1]) / lu, (gb2[2] - dot2 * b2[2]) / lu};
-                // u = a2 - d b1, d = b1 . a2
-                const float d = b1[0] * a[3] + b1[1] * a[4] + b1[2] * a[5];
-                const float gd = -(gu[0] * b1[0] + gu[1] * b1[1] + gu[2] * b1[2]);
-                float ga2[3] = {gu[0] + gd * b1[0], gu[1] + gd * b1[1], gu[2] + gd * b1[2]};
-#pragma unroll
-                for (int k = 0; k < 3; ++k) gb1[k] += -d * gu[k] + gd * a[3 + k];
-                // b1 = a1 / |a1|
-                const float dot1 = gb1[0] * b1[0] + gb1[1] * b1[1] + gb1[2] * b1[2];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { s[5 + k] = (gb1[k] - dot1 * b1[k]) / l1; s[8 + k] = ga2[k]; }
+                rot6d_bwd(a, R, l1, lu, gR, s + 5);
             }
             float mu = 0.f, sd = 0.f, dz;
             if (p.z_type == 3) { mu = p.z_stats[(c * p.bins + bin) * 2]; sd = p.z_stats[(c * p.bins + bin) * 2 + 1]; }
@@ -1144,41 +1136,20 @@ __global__ __launch_bounds__(64) void k_cube_select_param_bwd(CubeSelP pp, const
         }
     }
     __syncthreads();
-    float* g = g_raw + (size_t)i * p.ld;
-    for (int col = lane; col < p.ld; col += 64) {
-        float val = 0.f;
-        int e;
-        if ((e = col - (p.o_d2 + c * 2)) >= 0 && e < 2) val = s[e];
-        else if ((e = col - (p.o_dims + c * 3)) >= 0 && e < 3) val = s[2 + e];
-        else if ((e = col - (p.o_pose + c * pw)) >= 0 && e < pw) val = s[5 + e];
-        else if (col == zcol) val = s[CUBE_SEL_STAGE - 2];
-        else if (p.o_unc >= 0 && col == p.o_unc + c) val = s[CUBE_SEL_STAGE - 1];
-        g[col] = val;
-    }
+    select_scatter_row(p, c, zcol, pw, p.o_unc >= 0, s, g_raw + (size_t)i * p.ld, lane);
 }
 
-// the options and the layout against the row stride: every block [offset, offset + width * K) lies inside a row
+// cube_sel_fill with the three options
 static int cube_param_args(CubeSelP& pp, const char* who, const float* raw, int ld, const int* layout5, int K, int z_type, int bins,
                            const float* z_scales, const float* z_stats, const float* boxes, int pose_type, int dims_func,
                            const float* priors, const float* priors_std) {
-    CR_CHECK_ARG(raw && layout5 && K > 0 && bins >= 1 && ld > 0, "%s: bad sizes", who);
     CR_CHECK_ARG(pose_type >= 0 && pose_type <= 2, "%s: pose_type %d (0 6d, 1 quaternion, 2 euler)", who, pose_type);
     CR_CHECK_ARG(dims_func == 0 || (dims_func == 1 && priors && priors_std),
                  "%s: dims_func %d (0 exp, 1 sigmoid with the prior means and standard deviations)", who, dims_func);
-    CR_CHECK_ARG(z_type >= 0 && z_type <= 3, "%s: z_type %d (0 direct, 1 sigmoid, 2 log, 3 clusters)", who, z_type);
-    CR_CHECK_ARG(bins == 1 || (z_scales && boxes), "%s: CLUSTER_BINS > 1 needs the scale centres and the RoI boxes", who);
-    CR_CHECK_ARG(z_type != 3 || (bins > 1 && z_stats), "%s: Z_TYPE 'clusters' needs CLUSTER_BINS > 1 and the depth statistics", who);
-    const int pw = pose_type == 0 ? 6 : (pose_type == 1 ? 4 : 3);
-    const int64_t K64 = K;
-    CR_CHECK_ARG(layout5[0] >= 0 && layout5[0] + 2 * K64 <= ld && layout5[1] >= 0 && layout5[1] + 3 * K64 <= ld &&
-                     layout5[2] >= 0 && layout5[2] + pw * K64 <= ld && layout5[3] >= 0 && layout5[3] + bins * K64 <= ld &&
-                     (layout5[4] < 0 || layout5[4] + K64 <= ld),
-                 "%s: the predictor layout does not fit a row of %d columns", who, ld);
-    pp = CubeSelP{};
-    CubeSel& p = pp.s;
-    p.raw = raw; p.ld = ld; p.o_d2 = layout5[0]; p.o_dims = layout5[1]; p.o_pose = layout5[2]; p.o_z = layout5[3];
-    p.o_unc = layout5[4] < 0 ? -1 : layout5[4]; p.K = K; p.priors = priors; p.z_type = z_type; p.bins = bins;
-    p.z_scales = z_scales; p.z_stats = z_stats; p.boxes = boxes;
+    int rc = cube_sel_fill(pp.s, who, raw, ld, layout5, K, pose_type == 0 ? 6 : (pose_type == 1 ? 4 : 3), false, z_type, bins,
+                           z_scales, z_stats, boxes);
+    if (rc) return rc;
+    pp.s.priors = priors;
     pp.pose_type = pose_type; pp.dims_func = dims_func; pp.priors_std = priors_std;
     return CR_OK;
 }
@@ -1189,16 +1160,13 @@ extern "C" int cr_cube_select_param(cr_ctx* ctx, const float* raw, int ld, const
                                     unsigned char* validf, int* clsc, int z_type, int bins, const float* z_scales,
                                     const float* z_stats, const float* boxes, int pose_type, int dims_func,
                                     const float* priors_std, float* norm3) {
-    CR_CHECK_ARG(ctx && buf39 && validf && clsc && cls && valid && gt_idx && gt3d && gtpose && meta, "cr_cube_select_param: NULL pointer");
-    CR_CHECK_ARG(B > 0 && kf > 0 && kf <= S && G > 0, "cr_cube_select_param: bad sizes");
+    CR_CHECK_ARG(ctx && buf39 && validf && clsc, "cr_cube_select_param: NULL pointer");
     CubeSelP pp;
     int rc = cube_param_args(pp, "cr_cube_select_param", raw, ld, layout5, K, z_type, bins, z_scales, z_stats, boxes, pose_type,
                              dims_func, priors, priors_std);
+    if (!rc) rc = cube_sel_inputs(pp.s, "cr_cube_select_param", cls, valid, gt_idx, B, S, kf, G, gt3d, gtpose, priors, meta);
     if (rc) return rc;
-    CubeSel& p = pp.s;
-    p.cls = cls; p.valid = valid; p.gt_idx = gt_idx; p.S = S; p.kf = kf; p.G = G; p.n = B * kf;
-    p.gt3d = gt3d; p.gtpose = gtpose; p.meta = meta;
-    hipLaunchKernelGGL(k_cube_select_param, dim3((unsigned)cr_cdiv(p.n, 64)), dim3(64), 0, ctx->stream, pp, buf39, validf, clsc,
+    hipLaunchKernelGGL(k_cube_select_param, dim3((unsigned)cr_cdiv(pp.s.n, 64)), dim3(64), 0, ctx->stream, pp, buf39, validf, clsc,
                        norm3);
     CR_LAUNCH_CHECK();
     return CR_OK;

@@ -2329,12 +2329,15 @@ def _chunks(buf, n):
     return [buf[o * n:(o + d) * n] for o, d in zip(CUBE_OFF, CUBE_DIM)]
 
 
-def _cube_select(raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors, meta, boxes, zc, rows=39):
-    """forward plumbing of the two 3D-head loss Functions: cr_cube_select of raw (n,13K) into a fresh buffer of `rows` x n floats
-    whose first 39 rows are buf39 -> (raw32, the buffer, validf (n) uint8, clsc (n) int32, layout as c_int[5], boxes f32)"""
+def _cube_select(raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors, meta, boxes, zc, rows=39, param=None):
+    """the one place that marshals a forward selection of the 3D head: raw (n, ld) into a fresh buffer of `rows` x n floats whose
+    first 39 rows are buf39; with rows = 42 the last three are the `norm` rows of the non-disentangled loss.  param None: the
+    default family, cr_cube_select (+ cr_cube_select_norm for the norm rows); param = (pose code, dims code, priors_std):
+    cr_cube_select_param, which writes the norm rows itself.
+    -> (raw32, the buffer, validf (n) uint8, clsc (n) int32, boxes f32)"""
     _need_cuda(raw, "cube head output")
     B, S = cls.shape
-    n = B * kf
+    n, K, kf = B * kf, int(K), int(kf)
     dev = raw.device
     raw32 = raw.detach().float().contiguous()
     buf = torch.empty((rows * n,), dtype=f32, device=dev)
@@ -2342,10 +2345,18 @@ def _cube_select(raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors, m
     clsc = torch.empty((n,), dtype=torch.int32, device=dev)
     lay = (_ct.c_int * 5)(*[int(v) for v in layout])
     boxes = boxes.float().contiguous()
-    _lib.call("cr_cube_select", raw32, raw32.shape[1], lay, int(K), cls.contiguous(), valid.to(torch.uint8).contiguous(),
-              gt_idx.contiguous(), B, S, int(kf), gt3d.shape[1], gt3d.contiguous(), gtpose.contiguous(), priors,
-              meta.contiguous(), buf, validf, clsc, zc[0], zc[1], zc[2], zc[3], boxes)
-    return raw32, buf, validf, clsc, lay, boxes
+    norm = buf[39 * n:] if rows > 39 else None
+    cls, valid, gt_idx = cls.contiguous(), valid.to(torch.uint8).contiguous(), gt_idx.contiguous()
+    gt3d, gtpose, meta = gt3d.contiguous(), gtpose.contiguous(), meta.contiguous()
+    if param is None:
+        _lib.call("cr_cube_select", raw32, raw32.shape[1], lay, K, cls, valid, gt_idx, B, S, kf, gt3d.shape[1], gt3d, gtpose, priors,
+                  meta, buf, validf, clsc, zc[0], zc[1], zc[2], zc[3], boxes)
+        if norm is not None:
+            _lib.call("cr_cube_select_norm", raw32, raw32.shape[1], lay, K, B, kf, clsc, zc[0], zc[1], zc[2], zc[3], boxes, norm)
+    else:
+        _lib.call("cr_cube_select_param", raw32, raw32.shape[1], lay, K, cls, valid, gt_idx, B, S, kf, gt3d.shape[1], gt3d, gtpose,
+                  priors, meta, buf, validf, clsc, zc[0], zc[1], zc[2], zc[3], boxes, param[0], param[1], param[2], norm)
+    return raw32, buf, validf, clsc, boxes
 
 
 def _cube_loss_ins(buf, boxes, n):
@@ -2356,151 +2367,85 @@ def _cube_loss_ins(buf, boxes, n):
 
 
 def _cube_grads(n, dev, zraw=False):
-    """one buffer for what the loss backward kernels write, split: g_dxy, g_zr, g_dr, g_Ra, g_u (+ g_zraw)"""
+    """one buffer for what the loss backward kernels write, split: g_dxy, g_zr, g_dr, g_Ra, g_u (+ a 17th row: g_zraw, or the
+    weak head's zero g_usel)"""
     cuts = (0, 2, 3, 6, 15, 16) + ((17,) if zraw else ())
     g = torch.empty((cuts[-1] * n,), dtype=f32, device=dev)
     return [g[a * n:b * n] for a, b in zip(cuts, cuts[1:])]
 
 
-def _cube_select_bwd(raw32, layout, K, B, kf, validf, clsc, grads, g_usel, zc, boxes):
-    """backward plumbing of the two 3D-head loss Functions: cr_cube_select_bwd of the five decoded-quantity gradients and the
-    selected uncertainty's -> (g_raw like raw32, layout as c_int[5])"""
+def _cube_select_bwd(raw32, layout, K, B, kf, validf, clsc, grads, g_usel, zc, boxes, param=None, g_zraw=None):
+    """the one place that marshals a backward selection: the five decoded-quantity gradients, the selected uncertainty's and
+    g_zraw (n) or None, the non-disentangled z term's gradient w.r.t. the raw depth -> g_raw like raw32.  param None: the default
+    family, cr_cube_select_bwd (+ cr_cube_select_bwd_zraw for g_zraw); param = (pose code, dims code, priors, priors_std):
+    cr_cube_select_param_bwd, which adds g_zraw itself and takes NULL for a missing g_usel."""
     g_dxy, g_zr, g_dr, g_Ra, g_u = grads
     g_raw = torch.empty_like(raw32)
     lay = (_ct.c_int * 5)(*layout)
-    _lib.call("cr_cube_select_bwd", raw32, raw32.shape[1], lay, K, B, kf, validf, clsc, g_dxy, g_zr, g_dr, g_Ra, g_u,
-              g_usel.contiguous(), g_raw, zc[0], zc[1], zc[2], zc[3], boxes)
-    return g_raw, lay
+    if param is None:
+        _lib.call("cr_cube_select_bwd", raw32, raw32.shape[1], lay, K, B, kf, validf, clsc, g_dxy, g_zr, g_dr, g_Ra, g_u,
+                  g_usel.contiguous(), g_raw, zc[0], zc[1], zc[2], zc[3], boxes)
+        if g_zraw is not None:
+            _lib.call("cr_cube_select_bwd_zraw", raw32.shape[1], lay, K, B, kf, validf, clsc, g_zraw, g_raw, zc[1], zc[2], boxes)
+    else:
+        _lib.call("cr_cube_select_param_bwd", raw32, raw32.shape[1], lay, K, B, kf, validf, clsc, g_dxy, g_zr, g_dr, g_Ra, g_u,
+                  None if g_usel is None else g_usel.contiguous(), g_raw, zc[0], zc[1], zc[2], zc[3], boxes, param[0], param[1],
+                  param[2], param[3], g_zraw)
+    return g_raw
+
+
+_CubeRoute = _collections.namedtuple("_CubeRoute", "param disentangled flags")
 
 
 class _CubeHeadLoss(torch.autograd.Function):
-    """raw (n,13K) -> per-RoI losses (n,5), selected uncertainty (n); saves what the two backward kernels need."""
+    """raw (n, ld) -> per-RoI losses (n,5), selected uncertainty (n); saves what the two backward kernels need.  Four stages --
+    select, loss, loss backward, select backward -- whose entry points the route picks (_CubeRoute, computed by cube_head_loss):
+    param         an option off its default changes the predictor layout or the decode of a selected column (POSE_TYPE
+                  'quaternion' / 'euler', no uncertainty block, DIMS_PRIORS_FUNC 'sigmoid'): cr_cube_select_param / _param_bwd,
+                  else the default family cr_cube_select / _select_bwd
+    disentangled  cr_cube_loss_fwd / _bwd on buf39; else the non-disentangled losses (roi_heads.py:2516-2560),
+                  cr_cube_nondis_fwd / _bwd: three rows after the 39 carry the pre-decode depth and the cluster statistics, and the
+                  z term's gradient w.r.t. the raw depth reaches the depth column through the backward selection
+    flags         (allocentric, chamfer_pose, use_conf, joint, z config, pose code, dims code)"""
 
     @staticmethod
-    def forward(ctx, raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors, meta, boxes, flags):
+    def forward(ctx, raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors, priors_std, meta, boxes, route):
+        allocentric, chamfer_pose, use_conf, joint, zc, pose_code, dims_code = route.flags
         B, n = cls.shape[0], cls.shape[0] * kf
-        raw32, buf, validf, clsc, _, boxes = _cube_select(raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors, meta, boxes,
-                                                          flags[4])
+        raw32, buf_all, validf, clsc, boxes = _cube_select(raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors, meta, boxes, zc,
+                                                           rows=39 if route.disentangled else 42,
+                                                           param=(pose_code, dims_code, priors_std) if route.param else None)
+        buf, norm = buf_all[:39 * n], buf_all[39 * n:]
         ch, arr = _cube_loss_ins(buf, boxes, n)
         losses = torch.empty((n, 5), dtype=f32, device=raw.device)
         dec = torch.empty((n, 17), dtype=f32, device=raw.device)
-        _lib.call("cr_cube_loss_fwd", arr, n, *flags[:4], losses, dec)
-        ctx.keep = (raw32, buf, validf, clsc, boxes, tuple(layout), int(K), B, int(kf), flags, raw.dtype)
-        ctx.set_materialize_grads(False)       # outputs nobody differentiates arrive as None, not as zero fills
-        ctx.mark_non_differentiable(dec, buf, validf)
-        return losses, ch[4].clone(), dec, buf, validf
-
-    @staticmethod
-    def backward(ctx, gl, g_usel, _gd, _gb, _gv):
-        raw32, buf, validf, clsc, boxes, layout, K, B, kf, flags, dt = ctx.keep
-        n = B * kf
-        _, arr = _cube_loss_ins(buf, boxes, n)
-        grads = _cube_grads(n, raw32.device)
-        _lib.call("cr_cube_loss_bwd", arr, n, *flags[:4], gl.contiguous(), *grads)
-        g_raw, _ = _cube_select_bwd(raw32, layout, K, B, kf, validf, clsc, grads, g_usel, flags[4], boxes)
-        return (g_raw.to(dt),) + (None,) * 12
-
-
-class _CubeHeadLossNondis(torch.autograd.Function):
-    """_CubeHeadLoss with the non-disentangled losses (MODEL.ROI_CUBE_HEAD.DISENTANGLED_LOSS False, roi_heads.py:2516-2560): the
-    same select / reduce kernels around cr_cube_nondis_fwd / _bwd; three rows after the 39 of `buf` carry the pre-decode depth and
-    the cluster statistics, and the z term's gradient w.r.t. the raw depth is added to the depth column by its own launch."""
-
-    @staticmethod
-    def forward(ctx, raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, meta, boxes, flags):
-        B, n = cls.shape[0], cls.shape[0] * kf
-        zc = flags[3]
-        raw32, buf42, validf, clsc, lay, boxes = _cube_select(raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, None, meta, boxes,
-                                                              zc, rows=42)
-        buf, norm = buf42[:39 * n], buf42[39 * n:]
-        _lib.call("cr_cube_select_norm", raw32, raw32.shape[1], lay, int(K), B, int(kf), clsc, zc[0], zc[1], zc[2], zc[3],
-                  boxes, norm)
-        ch, arr = _cube_loss_ins(buf, boxes, n)
-        losses = torch.empty((n, 5), dtype=f32, device=raw.device)
-        dec = torch.empty((n, 17), dtype=f32, device=raw.device)
-        _lib.call("cr_cube_nondis_fwd", arr, norm, n, *flags[:3], zc[0], losses, dec)
-        ctx.keep = (raw32, buf42, validf, clsc, boxes, tuple(layout), int(K), B, int(kf), flags, raw.dtype)
-        ctx.set_materialize_grads(False)       # outputs nobody differentiates arrive as None, not as zero fills
-        ctx.mark_non_differentiable(dec, buf, validf)
-        return losses, ch[4].clone(), dec, buf, validf
-
-    @staticmethod
-    def backward(ctx, gl, g_usel, _gd, _gb, _gv):
-        raw32, buf42, validf, clsc, boxes, layout, K, B, kf, flags, dt = ctx.keep
-        n = B * kf
-        buf, norm = buf42[:39 * n], buf42[39 * n:]
-        _, arr = _cube_loss_ins(buf, boxes, n)
-        *grads, g_zraw = _cube_grads(n, raw32.device, zraw=True)
-        zc = flags[3]
-        _lib.call("cr_cube_nondis_bwd", arr, norm, n, *flags[:3], zc[0], gl.contiguous(), *grads, g_zraw)
-        g_raw, lay = _cube_select_bwd(raw32, layout, K, B, kf, validf, clsc, grads, g_usel, zc, boxes)
-        if zc[0] != 0:                         # 'direct' has no normalised depth space: its z term went through g_zr
-            _lib.call("cr_cube_select_bwd_zraw", raw32.shape[1], lay, K, B, kf, validf, clsc, g_zraw, g_raw, zc[1], zc[2],
-                      boxes)
-        return (g_raw.to(dt),) + (None,) * 11
-
-
-class _CubeHeadLossParam(torch.autograd.Function):
-    """_CubeHeadLoss / _CubeHeadLossNondis for the options that change the predictor layout or the decode of a selected column
-    (POSE_TYPE 'quaternion' / 'euler', no uncertainty block, DIMS_PRIORS_FUNC 'sigmoid'): cr_cube_select_param / _param_bwd around
-    the same loss kernels.  The selection writes the three `norm` rows of the non-disentangled loss itself and its backward adds
-    the raw-depth gradient, so both families take two launches each way."""
-
-    @staticmethod
-    def forward(ctx, raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors, priors_std, meta, boxes, flags):
-        allocentric, chamfer_pose, use_conf, joint, zc, disentangled, pose_code, dims_code = flags
-        _need_cuda(raw, "cube head output")
-        B, S = cls.shape
-        n = B * kf
-        dev = raw.device
-        raw32 = raw.detach().float().contiguous()
-        rows = 39 if disentangled else 42
-        buf_all = torch.empty((rows * n,), dtype=f32, device=dev)
-        buf, norm = buf_all[:39 * n], (None if disentangled else buf_all[39 * n:])
-        validf = torch.empty((n,), dtype=torch.uint8, device=dev)
-        clsc = torch.empty((n,), dtype=torch.int32, device=dev)
-        lay = (_ct.c_int * 5)(*[int(v) for v in layout])
-        boxes = boxes.float().contiguous()
-        _lib.call("cr_cube_select_param", raw32, raw32.shape[1], lay, int(K), cls.contiguous(),
-                  valid.to(torch.uint8).contiguous(), gt_idx.contiguous(), B, S, int(kf), gt3d.shape[1], gt3d.contiguous(),
-                  gtpose.contiguous(), priors, meta.contiguous(), buf, validf, clsc, zc[0], zc[1], zc[2], zc[3], boxes,
-                  pose_code, dims_code, priors_std, norm)
-        ch, arr = _cube_loss_ins(buf, boxes, n)
-        losses = torch.empty((n, 5), dtype=f32, device=dev)
-        dec = torch.empty((n, 17), dtype=f32, device=dev)
-        if disentangled:
+        if route.disentangled:
             _lib.call("cr_cube_loss_fwd", arr, n, allocentric, chamfer_pose, use_conf, joint, losses, dec)
         else:
             _lib.call("cr_cube_nondis_fwd", arr, norm, n, allocentric, use_conf, joint, zc[0], losses, dec)
-        ctx.keep = (raw32, buf_all, validf, clsc, boxes, priors, priors_std, tuple(int(v) for v in layout), int(K), B, int(kf), flags,
-                    raw.dtype)
+        ctx.keep = (raw32, buf_all, validf, clsc, boxes, priors, priors_std, layout, int(K), B, int(kf), route, raw.dtype)
         ctx.set_materialize_grads(False)       # outputs nobody differentiates arrive as None, not as zero fills
         ctx.mark_non_differentiable(dec, buf, validf)
         return losses, ch[4].clone(), dec, buf, validf
 
     @staticmethod
     def backward(ctx, gl, g_usel, _gd, _gb, _gv):
-        raw32, buf_all, validf, clsc, boxes, priors, priors_std, layout, K, B, kf, flags, dt = ctx.keep
-        allocentric, chamfer_pose, use_conf, joint, zc, disentangled, pose_code, dims_code = flags
+        raw32, buf_all, validf, clsc, boxes, priors, priors_std, layout, K, B, kf, route, dt = ctx.keep
+        allocentric, chamfer_pose, use_conf, joint, zc, pose_code, dims_code = route.flags
         n = B * kf
-        buf, norm = buf_all[:39 * n], (None if disentangled else buf_all[39 * n:])
+        buf, norm = buf_all[:39 * n], buf_all[39 * n:]
         _, arr = _cube_loss_ins(buf, boxes, n)
-        glc = gl.contiguous()
-        g_zraw = None
-        if disentangled:
-            g_dxy, g_zr, g_dr, g_Ra, g_u = _cube_grads(n, raw32.device)
-            _lib.call("cr_cube_loss_bwd", arr, n, allocentric, chamfer_pose, use_conf, joint, glc, g_dxy, g_zr, g_dr, g_Ra, g_u)
+        g_dxy, g_zr, g_dr, g_Ra, g_u, *g_zraw = _cube_grads(n, raw32.device, zraw=not route.disentangled)
+        if route.disentangled:
+            _lib.call("cr_cube_loss_bwd", arr, n, allocentric, chamfer_pose, use_conf, joint, gl.contiguous(), g_dxy, g_zr, g_dr, g_Ra,
+                      g_u)
         else:
-            g_dxy, g_zr, g_dr, g_Ra, g_u, g_zraw = _cube_grads(n, raw32.device, zraw=True)
-            _lib.call("cr_cube_nondis_bwd", arr, norm, n, allocentric, use_conf, joint, zc[0], glc, g_dxy, g_zr, g_dr, g_Ra, g_u,
-                      g_zraw)
-            if zc[0] == 0:                     # 'direct' has no normalised depth space: its z term went through g_zr
-                g_zraw = None
-        g_raw = torch.empty_like(raw32)
-        lay = (_ct.c_int * 5)(*layout)
-        _lib.call("cr_cube_select_param_bwd", raw32, raw32.shape[1], lay, K, B, kf, validf, clsc, g_dxy, g_zr, g_dr, g_Ra, g_u,
-                  None if g_usel is None else g_usel.contiguous(), g_raw, zc[0], zc[1], zc[2], zc[3], boxes, pose_code, dims_code,
-                  priors, priors_std, g_zraw)
+            _lib.call("cr_cube_nondis_bwd", arr, norm, n, allocentric, use_conf, joint, zc[0], gl.contiguous(), g_dxy, g_zr, g_dr, g_Ra,
+                      g_u, g_zraw[0])
+        # 'direct' has no normalised depth space: its z term went through g_zr
+        g_raw = _cube_select_bwd(raw32, layout, K, B, kf, validf, clsc, (g_dxy, g_zr, g_dr, g_Ra, g_u), g_usel, zc, boxes,
+                                 param=(pose_code, dims_code, priors, priors_std) if route.param else None,
+                                 g_zraw=g_zraw[0] if g_zraw and zc[0] != 0 else None)
         return (g_raw.to(dt),) + (None,) * 13
 
 
@@ -2519,26 +2464,20 @@ def cube_head_loss(raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, priors,
     With the default values of these three the entry points of the default family are launched, as before."""
     pose_code = pose_type_code(pose_type)
     dims_code = dims_func_code(dims_func, priors, priors_std)
-    if pose_code != 0 or dims_code != 0 or not use_conf:
-        if not disentangled and priors is not None:
-            raise ValueError("cube_head_loss: the non-disentangled loss is built without dimension priors "
-                             "(DIMS_PRIORS_ENABLED False): the reference fails with them (roi_heads.py:2532)")
-        lay = tuple(int(v) for v in layout[:4]) + (int(layout[4]) if use_conf else -1,)
-        flags = (int(bool(allocentric)), int(bool(chamfer_pose)), int(bool(use_conf)), int(bool(joint)), z_cfg or z_config(z_type),
-                 bool(disentangled), pose_code, dims_code)
+    if not disentangled and priors is not None:
+        raise ValueError("cube_head_loss: the non-disentangled loss is built without dimension priors "
+                         "(DIMS_PRIORS_ENABLED False): the reference fails with them (roi_heads.py:2532)")
+    route = _CubeRoute(pose_code != 0 or dims_code != 0 or not use_conf, bool(disentangled),
+                       (int(bool(allocentric)), int(bool(chamfer_pose)), int(bool(use_conf)), int(bool(joint)),
+                        z_cfg or z_config(z_type), pose_code, dims_code))
+    lay = tuple(int(v) for v in layout[:4]) + (int(layout[4]) if use_conf else -1,)
+    if route.param:
         f = lambda t: None if t is None else t.detach().float().contiguous()
-        return _CubeHeadLossParam.apply(raw, lay, K, cls, valid, gt_idx, kf, gt3d, gtpose.reshape(gtpose.shape[0], -1, 9),
-                                        f(priors), f(priors_std) if dims_code else None, meta, boxes, flags)
-    if not disentangled:
-        if priors is not None:
-            raise ValueError("cube_head_loss: the non-disentangled loss is built without dimension priors "
-                             "(DIMS_PRIORS_ENABLED False): the reference fails with them (roi_heads.py:2532)")
-        flags = (int(bool(allocentric)), int(bool(use_conf)), int(bool(joint)), z_cfg or z_config(z_type))
-        return _CubeHeadLossNondis.apply(raw, tuple(layout), K, cls, valid, gt_idx, kf, gt3d,
-                                         gtpose.reshape(gtpose.shape[0], -1, 9), meta, boxes, flags)
-    flags = (int(bool(allocentric)), int(bool(chamfer_pose)), int(bool(use_conf)), int(bool(joint)), z_cfg or z_config(z_type))
-    return _CubeHeadLoss.apply(raw, tuple(layout), K, cls, valid, gt_idx, kf, gt3d, gtpose.reshape(gtpose.shape[0], -1, 9),
-                               priors, meta, boxes, flags)
+        priors, priors_std = f(priors), f(priors_std) if dims_code else None
+    else:
+        priors_std = None
+    return _CubeHeadLoss.apply(raw, lay, K, cls, valid, gt_idx, kf, gt3d, gtpose.reshape(gtpose.shape[0], -1, 9), priors, priors_std,
+                               meta, boxes, route)
 
 
 def cube_decode_infer(raw, layout, K, cls, img, boxes, meta6, priors, allocentric=True, z_type="direct", z_cfg=None,
@@ -2547,24 +2486,21 @@ def cube_decode_infer(raw, layout, K, cls, img, boxes, meta6, priors, allocentri
     priors_std as in cube_head_loss; off their defaults the decode is cr_cube_decode_infer_param.  Without confidence column 8
     repeats column 7 (the reference's score merge reads the last column of its cube_3D, roi_heads.py:2693-2716)."""
     _need_cuda(raw, "cube head output")
-    n = raw.shape[0]
+    n, K, allocentric = raw.shape[0], int(K), int(bool(allocentric))
     out = torch.empty((n, 42), dtype=f32, device=raw.device)
     raw32 = raw.detach().float().contiguous()
     zc = z_cfg or z_config(z_type)
     pose_code = pose_type_code(pose_type)
     dims_code = dims_func_code(dims_func, priors, priors_std)
+    lay = (_ct.c_int * 5)(*[int(v) for v in layout[:4]], int(layout[4]) if use_conf else -1)
+    cls, img, boxes, meta6 = cls.contiguous(), img.to(torch.int32).contiguous(), boxes.float().contiguous(), meta6.contiguous()
     if pose_code != 0 or dims_code != 0 or not use_conf:
-        lay = (_ct.c_int * 5)(*([int(v) for v in layout[:4]] + [int(layout[4]) if use_conf else -1]))
         f = lambda t: None if t is None else t.detach().float().contiguous()
-        _lib.call("cr_cube_decode_infer_param", raw32, raw32.shape[1], lay, int(K), cls.contiguous(),
-                  img.to(torch.int32).contiguous(), boxes.float().contiguous(), meta6.contiguous(), f(priors), n,
-                  int(bool(allocentric)), out, zc[0], zc[1], zc[2], zc[3], pose_code, dims_code,
-                  f(priors_std) if dims_code else None)
-        return out
-    lay = (_ct.c_int * 5)(*[int(v) for v in layout])
-    _lib.call("cr_cube_decode_infer", raw32, raw32.shape[1], lay, int(K), cls.contiguous(), img.to(torch.int32).contiguous(),
-              boxes.float().contiguous(), meta6.contiguous(), priors, n, int(bool(allocentric)), out, zc[0], zc[1], zc[2],
-              zc[3])
+        _lib.call("cr_cube_decode_infer_param", raw32, raw32.shape[1], lay, K, cls, img, boxes, meta6, f(priors), n, allocentric, out,
+                  zc[0], zc[1], zc[2], zc[3], pose_code, dims_code, f(priors_std) if dims_code else None)
+    else:
+        _lib.call("cr_cube_decode_infer", raw32, raw32.shape[1], lay, K, cls, img, boxes, meta6, priors, n, allocentric, out, zc[0],
+                  zc[1], zc[2], zc[3])
     return out
 
 
@@ -2612,20 +2548,12 @@ class _WeakCubeLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, raw, layout, K, cls, valid, gt_idx, kf, gt_boxes, gt3d, gtpose, prior_mean, prior_std, meta, table, normals,
                 boxes, depth, terms, pgz_mode, weights, allocentric, zt):
-        _need_cuda(raw, "cube head output")
         B, S = cls.shape
         n, G = B * kf, gt3d.shape[1]
         dev = raw.device
-        raw32 = raw.detach().float().contiguous()
-        buf = torch.empty((39 * n,), dtype=f32, device=dev)
-        validf = torch.empty((n,), dtype=torch.uint8, device=dev)
-        clsc = torch.empty((n,), dtype=torch.int32, device=dev)
-        lay = (_ct.c_int * 5)(*[int(v) for v in layout])
-        cls, gt_idx, gt_boxes, table = cls.contiguous(), gt_idx.contiguous(), gt_boxes.float().contiguous(), table.contiguous()
-        boxes = boxes.float().contiguous()
-        _lib.call("cr_cube_select", raw32, raw32.shape[1], lay, int(K), cls, valid.to(torch.uint8).contiguous(), gt_idx, B, S,
-                  int(kf), G, gt3d.contiguous(), gtpose.contiguous(), prior_mean, meta.contiguous(), buf, validf, clsc, zt[0],
-                  zt[1], zt[2], zt[3], boxes)
+        cls, gt_idx = cls.contiguous(), gt_idx.contiguous()
+        raw32, buf, validf, clsc, boxes = _cube_select(raw, layout, K, cls, valid, gt_idx, kf, gt3d, gtpose, prior_mean, meta, boxes, zt)
+        gt_boxes, table = gt_boxes.float().contiguous(), table.contiguous()
         ch = _chunks(buf, n)
         ins = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in (ch[0], ch[1], ch[2], ch[3], ch[4], ch[6], ch[7], boxes)])
         out = torch.empty((n * (8 + 17 + 4 + 1 + 1) + 2 * B + 27,), dtype=f32, device=dev)
@@ -2672,16 +2600,12 @@ class _WeakCubeLoss(torch.autograd.Function):
         Lraw, dec, ztgt, pimg = out[:8 * n], out[8 * n:25 * n], out[29 * n:30 * n], out[31 * n:31 * n + 2 * B]
         tail = out[31 * n + 2 * B:]
         cnt, aux = tail[9:18], tail[26:27]
-        g = torch.empty((17 * n,), dtype=f32, device=dev)
-        g_dxy, g_zr, g_dr, g_Ra, g_u, zero = g[:2 * n], g[2 * n:3 * n], g[3 * n:6 * n], g[6 * n:15 * n], g[15 * n:16 * n], g[16 * n:]
+        g_dxy, g_zr, g_dr, g_Ra, g_u, zero = _cube_grads(n, dev, zraw=True)      # the 17th row: a zero g_usel
         zero.zero_()
         _lib.call("cr_weak_loss_bwd", ctypes.cast(ins, ctypes.c_void_p), validf, clsc, gt_idx, gt_boxes, prior_std, table,
                   normals, B, kf, S, G, allocentric, terms, gred.float().contiguous(), cnt, aux, Lraw, dec, ztgt, pimg, g_dxy,
                   g_zr, g_dr, g_Ra, g_u)
-        g_raw = torch.empty_like(raw32)
-        lay = (_ct.c_int * 5)(*layout)
-        _lib.call("cr_cube_select_bwd", raw32, raw32.shape[1], lay, K, B, kf, validf, clsc, g_dxy, g_zr, g_dr, g_Ra, g_u, zero,
-                  g_raw, zt[0], zt[1], zt[2], zt[3], boxes)
+        g_raw = _cube_select_bwd(raw32, layout, K, B, kf, validf, clsc, (g_dxy, g_zr, g_dr, g_Ra, g_u), zero, zt, boxes)
         return (g_raw.to(dt),) + (None,) * 21
 
 

@@ -259,12 +259,14 @@ def test_selection_depth_types_match_float64(z_type, bins):
 
 
 def test_param_kernels_on_the_default_options_match_the_old_kernels():
-    """6d / exp / confidence through cr_cube_select(_bwd), whose Gram-Schmidt backward exists a second time in
-    cr_cube_select_param_bwd (the old kernels' device code is pinned, so the copies have to be kept in step): the old kernels are
-    held to the same float64 definition at the same 4 x float32 floor as the new ones in test_selection_matches_float64, and the
-    copies, flags and zero patterns of old and new are identical.  Old and new are not compared to each other at a bound of their
-    own: the Gram-Schmidt of this case's nearly parallel pairs amplifies a different contraction of the same expression (measured:
-    they differ by 1.28e-6 of the scale where the float32 floor of the case is 5.67e-7, each within 4 x floor of float64)."""
+    """6d / exp / confidence through cr_cube_select(_bwd), the default family's own kernels, which share their device helpers
+    (rot6d, rot6d_bwd, the meta / ground-truth copy, the dense-row scatter) with cr_cube_select_param(_bwd) but stay separate
+    kernels because their output bits are pinned: the old kernels are held to the same float64 definition at the same 4 x float32
+    floor as the new ones in test_selection_matches_float64, and the copies, flags and zero patterns of old and new are identical.
+    Old and new are not compared to each other at a bound of their own: inside two different kernels the compiler contracts the
+    same source expression differently, and the Gram-Schmidt of this case's nearly parallel pairs amplifies that (measured: the
+    forward rotations differ by 1.28e-6 of the scale where the float32 floor of the case is 5.67e-7, each within 4 x floor of
+    float64)."""
     c = sel_case("6d", True)
     ref, gref, v, cl = sel_reference(c, "6d", "exp", True, torch.float64)
     f32, g32, _, _ = sel_reference(c, "6d", "exp", True, torch.float32)

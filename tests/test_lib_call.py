@@ -162,7 +162,7 @@ def _call_sites():
 
 
 # the call sites whose argument list expands a tuple: their arity is only bounded from above.  No new one may appear.
-MAX_STARRED_SITES = 7
+MAX_STARRED_SITES = 3
 
 
 def test_every_call_site_names_an_entry_point_with_the_headers_arity():

@@ -75,6 +75,8 @@ class FPN(Backbone):
         self.lateral_convs = lateral_convs[::-1]
         self.output_convs = output_convs[::-1]
         self.in_features = tuple(in_features)
+        if hasattr(bottom_up, "attach_laterals"):    # a trunk with a padded physical channel layout pads the lateral weights
+            bottom_up.attach_laterals(dict(zip(in_features, lateral_convs)))
         self.bottom_up = bottom_up
         self.top_block = top_block
         self._out_feature_strides = {"p{}".format(int(math.log2(s))): s for s in strides}
@@ -103,12 +105,15 @@ class FPN(Backbone):
         # launch per direction (ops.conv_bias_act_group): they are independent of each other, and alone the coarse levels
         # are a handful of tiles each
         lat0 = self.lateral_convs[0]
-        prev = ops.conv_bias_act(bottom_up_features[self.in_features[-1]], lat0.weight, lat0.bias, 1, 0)
+        # a trunk whose maps carry pad channels (ShuffleNetV2) supplies lateral weights with zero columns at the pads
+        lw = self.bottom_up.lateral_weights() if hasattr(self.bottom_up, "lateral_weights") else None
+        lat_w = (lambda i: self.lateral_convs[i].weight) if lw is None else (lambda i: lw[self.in_features[-i - 1]])
+        prev = ops.conv_bias_act(bottom_up_features[self.in_features[-1]], lat_w(0), lat0.bias, 1, 0)
         inner = [prev]
         for idx, lateral_conv in enumerate(self.lateral_convs):
             if idx > 0:
                 features = bottom_up_features[self.in_features[-idx - 1]]
-                lateral = ops.conv_bias_act(features, lateral_conv.weight, lateral_conv.bias, 1, 0)
+                lateral = ops.conv_bias_act(features, lat_w(idx), lateral_conv.bias, 1, 0)
                 prev = ops.upsample2x_add(lateral, prev)
                 if self._fuse_type == "avg":
                     prev = prev / 2

@@ -130,8 +130,9 @@ class FlatSGD:
         mode = ops.precision()
         bank = banks.get(mode)
         if bank is None:
+            # (_cr_no_bank: weights whose compute copies are made elsewhere -- the ShuffleNetV2 trunk pads its own)
             convs = [p for p in self.params if p.dim() == 4 and p.shape[2] == p.shape[3] and
-                     p.is_contiguous(memory_format=torch.channels_last)]
+                     p.is_contiguous(memory_format=torch.channels_last) and not getattr(p, "_cr_no_bank", False)]
             if not convs:
                 return None
             bank = banks[mode] = ops.WeightBank(convs, self.flat_p)     # in the precision mode of the process

@@ -1504,6 +1504,342 @@ def bn_act(x, bn, relu, stats=None):
     return _BNAct.apply(x, bn.weight, bn.bias, bn, relu, stats)
 
 
+# --------------------------------------------------------------------------
+# ShuffleNetV2 (csrc/shufflenet.hip): depthwise 3x3 convolution + BatchNorm, the unit tail (concat + channel shuffle in one
+# pass) and zero-padded compute copies of the parameters.  The trunk's activations live in a PADDED physical NHWC layout
+# (every branch width rounded up to a power of two, a two-half tensor stored as [half 0 | pad | half 1 | pad]) so that the
+# pointwise convolutions and BatchNorms run on the existing kernels; parameters, state dict and optimizer keep their logical
+# shapes.  Pad rows / columns / gamma / beta are exactly zero, so pad channels stay exactly zero forward and backward.
+# --------------------------------------------------------------------------
+def _dw_out_hw(H, W, stride):
+    return (H - 1) // stride + 1, (W - 1) // stride + 1
+
+
+def dwconv3x3_fwd_raw(x, w, stride, bias=None, stats=None):
+    """x NHWC f32 / bf16, w f32 with C * 9 elements in (C, 3, 3) order; stats: f32 [ceil(M/64)][2][C] rows for cr_bn_fwd"""
+    _need_cuda(x, "conv input")
+    assert x.is_contiguous() and x.dim() == 4 and w.dtype == f32
+    N, H, W, C = x.shape
+    Ho, Wo = _dw_out_hw(H, W, stride) if stride in (1, 2) else (H, W)
+    assert w.numel() == C * 9 and (bias is None or (bias.dtype == f32 and bias.numel() == C))
+    assert stats is None or (stats.dtype == f32 and stats.numel() >= (N * Ho * Wo + 63) // 64 * 2 * C)
+    y = torch.empty((N, Ho, Wo, C), dtype=x.dtype, device=x.device)
+    _lib.call("cr_dwconv3x3_fwd", x, w, y, N, H, W, C, stride, bias, stats, _af(x))
+    return y
+
+
+def dwconv3x3_bwd_data_raw(dy, w, in_shape, stride, accumulate=None):
+    """accumulate: as for conv_bwd_data_raw"""
+    N, H, W, C = in_shape
+    assert w.dtype == f32 and dy.is_contiguous() and w.numel() == C * 9
+    assert tuple(dy.shape) == (N,) + _dw_out_hw(H, W, stride) + (C,), "dy does not have the output's shape"
+    dx = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
+    if accumulate is not None:
+        assert tuple(accumulate.shape) == (N, H, W, C), "accumulate must have the input's shape"
+        accumulate = accumulate.to(dy.dtype).contiguous()
+    _lib.call("cr_dwconv3x3_bwd_data", dy, w, dx, N, H, W, C, stride, _af(dy), accumulate)
+    return dx
+
+
+def dw_wgrad_splits(M):
+    """pixel ranges of cr_dwconv3x3_bwd_weight (include/cr3dod.h): its workspace holds splits * C * 9 floats"""
+    rng = max(64, -(-M // 128))
+    return -(-M // rng)
+
+
+def dwconv3x3_bwd_weight_raw(dy, x, stride, sink=None):
+    """dW (C, 3, 3) f32, or added into `sink` (C * 9 floats) when given"""
+    N, H, W, C = x.shape
+    assert dy.dtype == x.dtype and dy.is_contiguous() and x.is_contiguous()
+    assert tuple(dy.shape) == (N,) + _dw_out_hw(H, W, stride) + (C,), "dy does not have the output's shape"
+    assert sink is None or (sink.dtype == f32 and sink.numel() == C * 9)
+    n_ws = dw_wgrad_splits(dy.shape[0] * dy.shape[1] * dy.shape[2]) * C * 9
+    ws = torch.empty((n_ws,), dtype=f32, device=x.device)
+    dw = sink if sink is not None else torch.empty((C, 3, 3), dtype=f32, device=x.device)
+    _lib.call("cr_dwconv3x3_bwd_weight", dy, x, dw, N, H, W, C, stride, int(sink is not None), _af(x), ws, n_ws)
+    return None if sink is not None else dw
+
+
+class _DwBN(torch.autograd.Function):
+    """depthwise 3x3 convolution + BatchNorm2d without a ReLU (every depthwise convolution of ShuffleNetV2): the structure of
+    _ConvBN -- train mode: statistics rows from the convolution, cr_bn_fwd / cr_bn_bwd; frozen statistics: the BatchNorm folded
+    into the nine taps (cr_fold_bn on the (C, 9) weight, made on every call from the live parameters) and cr_bn_frozen_unfold
+    in the backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, running_mean, running_var, stride, eps, momentum, training, slot=(None, 0)):
+        ctx.slot = slot
+        C = x.shape[3]
+        dev = x.device
+        if training:
+            _STATS_EPOCH[0] += 1
+            Ho, Wo = _dw_out_hw(x.shape[1], x.shape[2], stride)
+            M = x.shape[0] * Ho * Wo
+            nparts = (M + 63) // 64
+            stats = torch.empty((nparts, 2, C), dtype=f32, device=dev)
+            y_raw = dwconv3x3_fwd_raw(x, weight.detach(), stride, stats=stats)
+            out = torch.empty_like(y_raw)
+            mi = torch.empty((2, C), dtype=f32, device=dev)
+            _lib.call("cr_bn_fwd", y_raw, stats, nparts, gamma.detach(), beta.detach(), None, out, M, C, 0, float(eps),
+                      float(momentum), mi, running_mean, running_var, _af(x))
+        else:
+            wf32 = torch.empty((C, 9), dtype=f32, device=dev)
+            bias_f = torch.empty((C,), dtype=f32, device=dev)
+            _lib.call("cr_fold_bn", weight.detach(), gamma.detach(), beta.detach(), running_mean, running_var, float(eps), wf32,
+                      bias_f, C, 9, 1)
+            out = dwconv3x3_fwd_raw(x, wf32, stride, bias=bias_f)
+            y_raw, mi = wf32, None
+            ctx.frozen = (running_mean, running_var, float(eps))
+        ctx.cfg = (stride, training)
+        ctx.beta_ref = beta
+        ctx.save_for_backward(x, weight, gamma, y_raw, mi)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, weight, gamma, y_raw, mi = ctx.saved_tensors
+        stride, training = ctx.cfg
+        C = x.shape[3]
+        dev = x.device
+        dout = dout.to(x.dtype).contiguous()
+        gs, bs = grad_sink(gamma), grad_sink(ctx.beta_ref)
+        if gs is not None and bs is not None:
+            dgamma, dbeta, ret_g, ret_b = gs, bs, None, None
+        else:
+            dgamma = torch.zeros((C,), dtype=f32, device=dev)
+            dbeta = torch.zeros((C,), dtype=f32, device=dev)
+            ret_g, ret_b = dgamma, dbeta
+        need_dw = ctx.needs_input_grad[1]
+        wsink = grad_sink(weight) if need_dw else None
+        dw = None
+        if training:
+            M = y_raw.numel() // C
+            sums = torch.empty((1025, 2, C), dtype=f32, device=dev)
+            g = torch.empty_like(y_raw)
+            _lib.call("cr_bn_bwd", dout, None, y_raw, mi, gamma.detach(), sums, g, None, dgamma, dbeta, M, C, 0, _af(x))
+            w_bwd = weight.detach()
+            if need_dw:
+                dw = dwconv3x3_bwd_weight_raw(g, x, stride, wsink)
+        else:
+            running_mean, running_var, eps = ctx.frozen
+            g, w_bwd = dout, y_raw                           # y_raw: the folded taps
+            M = g.numel() // C
+            sg = torch.zeros((C,), dtype=f32, device=dev)
+            ws = torch.empty((1024, C), dtype=f32, device=dev)
+            _lib.call("cr_colsum_accum", g, int(g.dtype == f32), M, C, ws, sg)
+            dwf = dwconv3x3_bwd_weight_raw(g, x, stride)
+            if need_dw and wsink is None:
+                dw = dwf                                    # scaled in place
+            dst = wsink if wsink is not None else dw
+            _lib.call("cr_bn_frozen_unfold", dwf, sg, weight.detach(), gamma.detach(), running_mean, running_var, eps, dst,
+                      int(wsink is not None), dgamma, dbeta, C, 9)
+        dx = None
+        xslot, xi = ctx.slot
+        if ctx.needs_input_grad[0]:
+            if xslot is not None and xi > 1:                # not the first consumer of x: leave the contribution in the slot
+                _slot_put(xslot, dwconv3x3_bwd_data_raw(g, w_bwd, x.shape, stride, accumulate=_slot_fold(xslot)))
+            else:
+                dx = dwconv3x3_bwd_data_raw(g, w_bwd, x.shape, stride,
+                                            accumulate=_slot_take(xslot) if xslot is not None else None)
+        elif xslot is not None:
+            raise RuntimeError("gradient slot registered for an input that needs no gradient")
+        if dw is not None:
+            dw = dw.view(weight.shape)
+        return dx, dw, ret_g, ret_b, None, None, None, None, None, None, None
+
+
+def dwconv_bn(x, weight, gamma, beta, running_mean, running_var, stride=1, eps=1e-5, momentum=0.1, training=True):
+    """BatchNorm(depthwise_conv3x3(x)); weight: f32, C * 9 elements in (C, 3, 3) order (a (C,1,3,3) parameter or a padded
+    (C, 9) compute copy)"""
+    _need_cuda(x, "conv input")
+    return _DwBN.apply(x, weight, gamma, beta, running_mean, running_var, stride, eps, momentum, bool(training),
+                       _slot_register(x, False))
+
+
+def conv_bn_act_live(x, weight, gamma, beta, running_mean, running_var, stride=1, pad=0, relu=True, eps=1e-5, momentum=0.1,
+                     training=True):
+    """conv_bn_act without the inference fold cache: with frozen statistics the fold is made on every call from the tensors
+    handed in.  For compute copies that a kernel rewrites in place (PaddedPack) -- their version counters never move."""
+    xs = _slot_register(x, True)
+    return _ConvBN.apply(x, as_krsc(weight), gamma, beta, None, running_mean, running_var, stride, pad, relu, eps, momentum,
+                         bool(training), (xs, (None, 0)), 1)
+
+
+class _ShuffleTail(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, bf, slot=(None, 0)):
+        N, H, W, wp = b.shape
+        assert a.is_contiguous() and b.is_contiguous() and a.dtype == b.dtype and tuple(a.shape[:3]) == (N, H, W)
+        y = torch.empty((N, H, W, 2 * wp), dtype=b.dtype, device=b.device)
+        _lib.call("cr_shuffle_tail_fwd", a, a.shape[3], b, y, N * H * W, bf, wp, _af(b))
+        ctx.cfg = (bf, a.shape[3], slot)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        bf, aw, (slot, si) = ctx.cfg
+        dy = dy.contiguous()
+        N, H, W, wp2 = dy.shape
+        da = torch.empty((N, H, W, aw), dtype=dy.dtype, device=dy.device)
+        db = torch.empty((N, H, W, wp2 // 2), dtype=dy.dtype, device=dy.device)
+        _lib.call("cr_shuffle_tail_bwd", dy, da, aw, db, N * H * W, bf, wp2 // 2, _af(dy))
+        if slot is not None:                                # the unit input's first consumer (a convolution) adds this
+            _slot_put(slot, da)
+            da = None
+        return da, db, None, None
+
+
+def shuffle_tail(a, b, bf):
+    """channel_shuffle(cat(a[..., :bf], b[..., :bf]), 2) of a ShuffleNetV2 unit in one pass -> (N, H, W, 2 * wp) in the
+    two-half layout, pads zero.  a: the other branch (N, H, W, wp), or the unit's input (N, H, W, 2 * wp) whose first half
+    passes through; b (N, H, W, wp).  The gradient of a is zero beyond its first bf channels."""
+    _need_cuda(b, "unit tail input")
+    return _ShuffleTail.apply(a, b, bf, _slot_register(a, False))
+
+
+class _PackFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pack, *tensors):
+        ctx.set_materialize_grads(False)
+        ctx.pack = pack
+        outs = pack._forward(tensors, any(ctx.needs_input_grad))
+        ctx.gflat, ctx.srcs = pack._gflat, tensors
+        ctx.mark_non_differentiable(*[o for o, e in zip(outs, pack.entries) if not e["grad"]])
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        return (None,) + tuple(ctx.pack._backward(ctx.gflat, ctx.srcs, grads, ctx.needs_input_grad[1:]))
+
+
+class PaddedPack:
+    """Zero-padded float32 compute copies of a set of parameters / buffers, made by ONE launch (cr_padded_pack) on every call
+    of run() -- inside a captured graph it is a node of the graph, so replays follow the optimizer -- and their gradients
+    gathered back by one launch.
+
+    entries: dicts {"get": callable -> logical tensor, "rows": (halves, wl, wp), "cols": (halves, wl, wp[, leading halves that
+    are pads altogether and have no logical columns]), "shape": shape of
+    the padded view, "perm": optional permutation applied to it, "grad": bool, "T": bool (also the transposed copy, seeded as
+    the f32 backward-data layout of a 1x1 convolution)}; the logical tensor is a (halves_r * wl_r, halves_c * wl_c) matrix
+    in memory (include/cr3dod.h, cr_pdesc).  run() -> the padded tensors.  With gradients enabled every padded tensor of a "grad" entry carries a
+    gradient sink (grad_sink) in a zeroed flat buffer; the pack's backward -- autograd runs it after every consumer --
+    adds the logical part of that buffer into the logical tensors' own sinks (or returns it where they have none)."""
+
+    def __init__(self, entries):
+        self.entries = list(entries)
+        off = offT = 0
+        self.offs = []
+        for e in self.entries:
+            rp, cp = e["rows"][0] * e["rows"][2], e["cols"][0] * e["cols"][2]
+            self.offs.append((off, offT if e.get("T") else -1, rp, cp))
+            off += (rp * cp + 3) // 4 * 4
+            if e.get("T"):
+                offT += (rp * cp + 3) // 4 * 4
+        self.total, self.totalT = off, max(offT, 4)
+        self._ptrs = self._gptrs = None
+        self._gflat = None
+
+    def _descs(self, ptrs, idx, dev):
+        import numpy as np
+        dt = np.dtype([("logical", "<u8"), ("phys_off", "<i8"), ("physT_off", "<i8"), ("rows_p", "<i4"), ("cols_p", "<i4"),
+                       ("cols_l", "<i4"), ("row_wl", "<i4"), ("row_wp", "<i4"), ("col_wl", "<i4"), ("col_wp", "<i4"),
+                       ("col_skip", "<i4")])
+        assert dt.itemsize == 56
+        recs = []
+        for i, ptr in zip(idx, ptrs):
+            e, (off, offT, rp, cp) = self.entries[i], self.offs[i]
+            skip = e["cols"][3] if len(e["cols"]) > 3 else 0
+            recs.append((ptr, off, offT, rp, cp, (e["cols"][0] - skip) * e["cols"][1], e["rows"][1], e["rows"][2], e["cols"][1],
+                         e["cols"][2], skip))
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.CrError("PaddedPack: the parameters moved; run the model once before capturing a graph")
+        return torch.from_numpy(np.array(recs, dtype=dt).view(np.uint8).copy()).to(dev)
+
+    def _check(self, t, e):
+        n = e["rows"][0] * e["rows"][1] * (e["cols"][0] - (e["cols"][3] if len(e["cols"]) > 3 else 0)) * e["cols"][1]
+        _need_cuda(t, "PaddedPack")
+        if t.dtype != f32 or t.numel() != n:
+            raise _lib.CrError(f"PaddedPack: expected {n} float32 elements, got {tuple(t.shape)} {t.dtype}")
+        if not (t.is_contiguous(memory_format=torch.channels_last) if t.dim() == 4 else t.is_contiguous()):
+            raise _lib.CrError("PaddedPack: conv weights must be channels_last, everything else contiguous")
+
+    def run(self):
+        tensors = [e["get"]() for e in self.entries]
+        outs = _PackFn.apply(self, *tensors)
+        gflat = self._gflat
+        epoch = _WEIGHT_EPOCH[0]
+        for o, e, (off, offT, rp, cp) in zip(outs, self.entries, self.offs):
+            if gflat is not None and e["grad"]:
+                o._cr_grad = self._view(gflat, off, rp, cp, e)
+            if offT >= 0:                                   # the backward-data layout [Cin][Cout] of a 1x1 convolution (f32 modes)
+                o._cr_wcache32 = [(o._version, epoch, o.data_ptr()), o.detach(), self.wT[offT:offT + rp * cp].view(cp, rp)]
+        return outs
+
+    @staticmethod
+    def _view(flat, off, rp, cp, e):
+        v = flat[off:off + rp * cp].view(e["shape"])
+        return v.permute(e["perm"]) if e.get("perm") else v
+
+    def _forward(self, tensors, grad):
+        dev = tensors[0].device
+        ptrs = tuple(t.data_ptr() for t in tensors)
+        if ptrs != self._ptrs:
+            for t, e in zip(tensors, self.entries):
+                self._check(t, e)
+            self.descs = self._descs(ptrs, range(len(ptrs)), dev)
+            if getattr(self, "wflat", None) is None or self.wflat.device != dev:
+                self.wflat = torch.zeros((self.total,), dtype=f32, device=dev)
+                self.wT = torch.zeros((self.totalT,), dtype=f32, device=dev)
+            self._ptrs = ptrs
+        _lib.call("cr_padded_pack", self.descs, len(ptrs), self.wflat, self.wT, 0)
+        self._gflat = torch.zeros((self.total,), dtype=f32, device=dev) if grad else None
+        return [self._view(self.wflat, off, rp, cp, e) for e, (off, offT, rp, cp) in zip(self.entries, self.offs)]
+
+    def _backward(self, gflat, srcs, grads, need):
+        """-> the gradients of the logical tensors (None where they went into a sink)"""
+        wgrad_flush()                                       # queued weight gradients (deferred_wgrad) target gflat
+        idx = [i for i, e in enumerate(self.entries) if e["grad"] and need[i]]
+        if gflat is None or not idx:
+            return [None] * len(srcs)
+        for i, g in enumerate(grads):                       # whatever came back through plain autograd
+            if g is not None:
+                off, _, rp, cp = self.offs[i]
+                self._view(gflat, off, rp, cp, self.entries[i]).add_(g)
+        sinks = [grad_sink(srcs[i]) for i in idx]
+        ret = [None] * len(srcs)
+        if any(s is None for s in sinks):
+            tmp = torch.zeros((sum(srcs[i].numel() for i in idx),), dtype=f32, device=gflat.device)
+            o = 0
+            for k, i in enumerate(idx):
+                n = srcs[i].numel()
+                if sinks[k] is None:
+                    v = tmp[o:o + n]
+                    s = srcs[i]
+                    ret[i] = v.view(s.shape[0], s.shape[2], s.shape[3], s.shape[1]).permute(0, 3, 1, 2) if s.dim() == 4 \
+                        else v.view(s.shape)
+                    sinks[k] = ret[i]
+                o += n
+        gptrs = tuple(s.data_ptr() for s in sinks)
+        if gptrs != self._gptrs or any(r is not None for r in ret):
+            gdescs = self._descs(gptrs, idx, gflat.device)
+            if all(r is None for r in ret):
+                self._gptrs, self._gdescs = gptrs, gdescs
+        else:
+            gdescs = self._gdescs
+        _lib.call("cr_padded_pack", gdescs, len(idx), gflat, None, 2)
+        return ret
+
+    def unpack(self, which):
+        """logical = padded for the entries `which` (indices): the running statistics the BatchNorm kernels updated in
+        their padded copies"""
+        key = tuple(which)
+        cache = self.__dict__.setdefault("_udescs", {})
+        ent = cache.get(key)
+        if ent is None or ent[0] is not self._ptrs:
+            ent = cache[key] = (self._ptrs, self._descs([self._ptrs[i] for i in key], key, self.wflat.device))
+        _lib.call("cr_padded_pack", ent[1], len(key), self.wflat, None, 1)
+
+
 class _UpsampleAdd(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lat, top, slot=(None, 0)):

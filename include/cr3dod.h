@@ -516,6 +516,46 @@ int cr_dense_bn_bwd(cr_ctx* ctx, const void* da, const void* x, int64_t M, int64
 int cr_avgpool2x2_fwd(cr_ctx* ctx, const void* x, void* y, int N, int H, int W, int C, int act_f32);
 int cr_avgpool2x2_bwd(cr_ctx* ctx, const void* dy, void* dx, int N, int H, int W, int C, int act_f32);
 
+/* ---- ShuffleNetV2 trunk (3dod_amd/csrc/shufflenet.hip; the reference's cubercnn/modeling/backbone/shufflenet.py:22-43 takes
+ * torchvision's shufflenet_v2_x1_0 [third-party]) ------------------------------------------------------------------------
+ * Depthwise 3x3 convolution: nn.Conv2d(C, C, 3, stride, padding=1, groups=C, bias=False).  Direct convolution on the
+ * vector ALU, f32 accumulation; stride in {1,2}, C % 8 == 0, any N, H, W >= 1; anything else returns CR_EINVAL without a
+ * launch.  x / y / dy / dx / accumulate NHWC bf16 or f32 (act_f32 != 0); w f32 (C, 3, 3) in every precision mode and in
+ * all three directions.  Ho = (H - 1) / stride + 1, likewise Wo; M = N * Ho * Wo.
+ *   fwd         y = conv(x, w) + bias?; stats: optional f32 [ceil(M/64)][2][C], per 64 output pixels the per-channel sum /
+ *               sum of squares of the stored output -- the layout cr_bn_fwd reads (every entry written, fixed order).
+ *   bwd_data    dx = conv^T(dy, w) + accumulate?.
+ *   bwd_weight  dw (C, 3, 3) = (accumulate ? dw : 0) + sum_p dy x.  No atomics: pixel range s of
+ *               splits = ceil(M / max(64, ceil(M/128))) writes its partial sums into ws, which must hold splits * C * 9
+ *               floats (ws_floats), and a second pass adds the ranges in index order: bit-identical from run to run. */
+int cr_dwconv3x3_fwd(cr_ctx* ctx, const void* x, const float* w, void* y, int N, int H, int W, int C, int stride,
+                     const float* bias, float* stats, int act_f32);
+int cr_dwconv3x3_bwd_data(cr_ctx* ctx, const void* dy, const float* w, void* dx, int N, int H, int W, int C, int stride,
+                          int act_f32, const void* accumulate);
+int cr_dwconv3x3_bwd_weight(cr_ctx* ctx, const void* dy, const void* x, float* dw, int N, int H, int W, int C, int stride,
+                            int accumulate, int act_f32, float* ws, int64_t ws_floats);
+/* Tail of a ShuffleNetV2 unit: channel_shuffle(cat(a, b), groups = 2) in one pass.  a (M, lda) [its first bf channels are
+ * read; lda >= bf], b (M, wp), both halves of bf logical channels.  y (M, 2 * wp): logical channel c = 2 * j + g (g = 0: a[j],
+ * g = 1: b[j]) is stored at physical channel (c / bf) * wp + c % bf; the wp - bf pad channels of either half are written
+ * as zero.  wp % 8 == 0.  bwd: da (M, aw) [aw % 8 == 0, aw >= bf] and db (M, wp) from dy (M, 2 * wp); channels >= bf of
+ * both are written as zero (aw = 2 * wp gives the gradient of a unit input whose first half passed through). */
+int cr_shuffle_tail_fwd(cr_ctx* ctx, const void* a, int64_t lda, const void* b, void* y, int64_t M, int bf, int wp,
+                        int act_f32);
+int cr_shuffle_tail_bwd(cr_ctx* ctx, const void* dy, void* da, int aw, void* db, int64_t M, int bf, int wp, int act_f32);
+/* Zero-padded compute copies of float32 parameters, any number of tensors per launch.  Every tensor is a logical
+ * (rows, cols_l) matrix whose padded copy (rows_p, cols_p) lives at base + phys_off.  Along either axis a physical index i
+ * maps to logical index (i / wp) * wl + i % wp when i % wp < wl and is a pad otherwise (wl = logical, wp = padded width of
+ * one half; a plain tensor is one half); along the columns the first col_skip halves are pads altogether and the logical
+ * index is ((i / wp) - col_skip) * wl + i % wp (the 1x1 convolution that reads only the second half of a unit's input).
+ * mode 0: padded = logical, pads = 0, and where physT_off >= 0 also the transpose (cols_p, rows_p) at baseT + physT_off;
+ * mode 1: logical = padded; mode 2: logical += padded (pads are dropped). */
+typedef struct cr_pdesc {
+    void* logical;
+    int64_t phys_off, physT_off;
+    int rows_p, cols_p, cols_l, row_wl, row_wp, col_wl, col_wp, col_skip;
+} cr_pdesc;
+int cr_padded_pack(cr_ctx* ctx, const void* descs_dev, int ndesc, float* base, float* baseT, int mode);
+
 /* FC weights of the RoI heads (roi_heads.py:2160-2204, cube_head.py:152-202).  w f32 (O, C, HW) in the checkpoint's
  * (c,h,w) column order -> wb bf16 (O, HW, C) for NHWC-flattened inputs (HW = 1: plain cast); and the transpose for the
  * gradient: acc f32 (O, C, HW) += g bf16 (O, HW, C). */

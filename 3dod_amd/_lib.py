@@ -140,6 +140,11 @@ SIGNATURES = {
     "cr_shuffle_tail_fwd": [P, P, c_int64, P, P, c_int64, c_int, c_int, c_int],
     "cr_shuffle_tail_bwd": [P, P, P, c_int, P, c_int64, c_int, c_int, c_int],
     "cr_padded_pack": [P, P, c_int, P, P, c_int],
+    "cr_dwconv_fwd": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_int],
+    "cr_dwconv_bwd_data": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
+    "cr_dwconv_bwd_weight": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int64],
+    "cr_bn_bwd_anyc": [P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int, c_int, c_int],
+    "cr_colsum_wide": [P, P, c_int64, c_int, P, P, c_int],
     "cr_cube_decode_infer": [P, P, c_int, P, c_int, P, P, P, P, P, c_int, c_int, P, c_int, c_int, P, P],
     "cr_cube_select_param": [P, P, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, c_int, c_int, P, P, P,
                              c_int, c_int, P, P],

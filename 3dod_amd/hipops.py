@@ -462,9 +462,12 @@ def conv_bwd_weight_raw(dy, x, k, stride, pad, sink=None, bias_acc=None):
 class _ConvBN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, gamma, beta, residual, running_mean, running_var, stride, pad, relu, eps, momentum,
-                training, slots=((None, 0), (None, 0)), groups=1):
+                training, slots=((None, 0), (None, 0)), groups=1, wide_sums=False):
         ctx.slots = slots
         ctx.groups = groups
+        # wide_sums (the MNASNet trunk): every per-channel sum of the backward is added across threads in double -- the
+        # BatchNorm backward is cr_bn_bwd_anyc at every width, the frozen backward's bias sum cr_colsum_wide
+        ctx.wide_sums = wide_sums
         Cout, Cin, k, _ = weight.shape
         dev = x.device
         af = _af(x)
@@ -532,9 +535,11 @@ class _ConvBN(torch.autograd.Function):
         dev = x.device
         dout = dout.to(x.dtype).contiguous()
         M = y_raw.numel() // Cout
-        sums = torch.empty((1025, 2, Cout), dtype=f32, device=dev)
-        dx_raw = torch.empty_like(y_raw)
-        dres = torch.empty_like(y_raw) if has_res else None
+        anyc = bn_needs_anyc(Cout) or (ctx.wide_sums and not (has_res and relu))
+        if not anyc:
+            sums = torch.empty((1025, 2, Cout), dtype=f32, device=dev)
+            dx_raw = torch.empty_like(y_raw)
+            dres = torch.empty_like(y_raw) if has_res else None
         gs, bs = grad_sink(gamma), grad_sink(ctx.beta_ref)
         if gs is not None and bs is not None:
             dgamma, dbeta, ret_g, ret_b = gs, bs, None, None
@@ -542,7 +547,14 @@ class _ConvBN(torch.autograd.Function):
             dgamma = torch.zeros((Cout,), dtype=f32, device=dev)
             dbeta = torch.zeros((Cout,), dtype=f32, device=dev)
             ret_g, ret_b = dgamma, dbeta
-        if relu and not has_res:
+        if anyc:
+            # a width beyond cr_bn_bwd, or wide sums asked for (MNASNet): cr_bn_bwd_anyc has no dres output -- without a ReLU
+            # the residual's gradient is dout itself
+            if has_res and relu:
+                raise _lib.CrError(f"BatchNorm backward over {Cout} channels: residual + ReLU needs 256 % (C / 8) == 0")
+            dx_raw = bn_bwd_anyc_raw(dout, None, y_raw, mi, gamma.detach(), ctx.beta_ref.detach(), relu, dgamma, dbeta)
+            dres = dout if has_res else None
+        elif relu and not has_res:
             _lib.call("cr_bn_bwd_mask", dout, None, y_raw, mi, gamma.detach(), ctx.beta_ref.detach(), sums, dx_raw, None, dgamma,
                       dbeta, M, Cout, 1, _af(x))
         else:
@@ -574,7 +586,7 @@ class _ConvBN(torch.autograd.Function):
             dw = conv_grouped_bwd_weight_raw(dx_raw, x, groups, stride, grad_sink(weight))
         if root:
             return dx_raw, dw, ret_g, ret_b
-        return dx, dw, ret_g, ret_b, dres, None, None, None, None, None, None, None, None, None, None
+        return dx, dw, ret_g, ret_b, dres, None, None, None, None, None, None, None, None, None, None, None
 
     @staticmethod
     def _frozen_backward(ctx, dout, need_dx, need_dw, root):
@@ -616,7 +628,10 @@ class _ConvBN(torch.autograd.Function):
             raise RuntimeError("gradient slot registered for an input that needs no gradient")
         # dgamma needs <dwf, w> even when the weight itself needs no gradient; sum_p g rides on the weight-gradient launch
         sg = torch.zeros((Cout,), dtype=f32, device=dev)
-        if groups == 1:
+        if ctx.wide_sums and groups == 1:                  # the sum in a pass of its own, added in double
+            colsum_wide_raw(g, sg)
+            dwf = conv_bwd_weight_raw(g, x, k, stride, pad, None)
+        elif groups == 1:
             dwf = conv_bwd_weight_raw(g, x, k, stride, pad, None, bias_acc=sg)
         else:
             dwf = conv_grouped_bwd_weight_raw(g, x, groups, stride, None, bias_acc=sg)
@@ -637,7 +652,7 @@ class _ConvBN(torch.autograd.Function):
                   int(wsink is not None), dgamma, dbeta, Cout, K_)
         if root:
             return g, dw, ret_g, ret_b
-        return dx, dw, ret_g, ret_b, dres, None, None, None, None, None, None, None, None, None, None
+        return dx, dw, ret_g, ret_b, dres, None, None, None, None, None, None, None, None, None, None, None
 
 
 class _RootConvBN(torch.autograd.Function):
@@ -1657,12 +1672,17 @@ def dwconv_bn(x, weight, gamma, beta, running_mean, running_var, stride=1, eps=1
 
 
 def conv_bn_act_live(x, weight, gamma, beta, running_mean, running_var, stride=1, pad=0, relu=True, eps=1e-5, momentum=0.1,
-                     training=True):
+                     training=True, residual=None, wide_sums=False):
     """conv_bn_act without the inference fold cache: with frozen statistics the fold is made on every call from the tensors
-    handed in.  For compute copies that a kernel rewrites in place (PaddedPack) -- their version counters never move."""
+    handed in.  For compute copies that a kernel rewrites in place (PaddedPack) -- their version counters never move.
+    residual: added in the BatchNorm pass (train) or the convolution's epilogue (frozen); its gradient goes through the
+    gradient slot of the tensor when that tensor's first consumer was a convolution.  wide_sums: the backward forms its
+    per-channel sums with cr_bn_bwd_anyc / cr_colsum_wide (added across threads in double) at every width instead of
+    cr_bn_bwd / the weight gradient's bias sum, which add a block's rows one after the other in float32."""
     xs = _slot_register(x, True)
-    return _ConvBN.apply(x, as_krsc(weight), gamma, beta, None, running_mean, running_var, stride, pad, relu, eps, momentum,
-                         bool(training), (xs, (None, 0)), 1)
+    rs = _slot_register(residual, False) if residual is not None else (None, 0)
+    return _ConvBN.apply(x, as_krsc(weight), gamma, beta, residual, running_mean, running_var, stride, pad, relu, eps, momentum,
+                         bool(training), (xs, rs), 1, bool(wide_sums))
 
 
 class _ShuffleTail(torch.autograd.Function):
@@ -1838,6 +1858,180 @@ class PaddedPack:
         if ent is None or ent[0] is not self._ptrs:
             ent = cache[key] = (self._ptrs, self._descs([self._ptrs[i] for i in key], key, self.wflat.device))
         _lib.call("cr_padded_pack", ent[1], len(key), self.wflat, None, 1)
+
+
+# --------------------------------------------------------------------------
+# MNASNet (csrc/mnasnet.hip): depthwise k x k convolution (k in {3, 5}) + BatchNorm (+ ReLU), and the BatchNorm backward for
+# any C % 8 == 0 (cr_bn_bwd_anyc) that the trunk's widths (48, 80, 96, 192, 240, 320, 480, 576, 1152) need:
+# cr_bn_bwd / cr_bn_bwd_mask take 256 % (C / 8) == 0 only.  The trunk's activations live in the padded physical layout of the
+# ShuffleNetV2 trunk with single-half maps (every width rounded up to a multiple of 16); PaddedPack makes the compute copies.
+# --------------------------------------------------------------------------
+def dwconv_fwd_raw(x, w, k, stride, bias=None, stats=None, relu=False):
+    """x NHWC f32 / bf16, w f32 with C * k * k elements in (C, k, k) order; stats: f32 [ceil(M/64)][2][C] rows for cr_bn_fwd"""
+    _need_cuda(x, "conv input")
+    assert x.is_contiguous() and x.dim() == 4 and w.dtype == f32
+    N, H, W, C = x.shape
+    Ho, Wo = _dw_out_hw(H, W, stride) if stride in (1, 2) else (H, W)
+    assert w.numel() == C * k * k and (bias is None or (bias.dtype == f32 and bias.numel() == C))
+    assert stats is None or (stats.dtype == f32 and stats.numel() >= (N * Ho * Wo + 63) // 64 * 2 * C)
+    y = torch.empty((N, Ho, Wo, C), dtype=x.dtype, device=x.device)
+    _lib.call("cr_dwconv_fwd", x, w, y, N, H, W, C, k, stride, bias, stats, int(relu), _af(x))
+    return y
+
+
+def dwconv_bwd_data_raw(dy, w, in_shape, k, stride, accumulate=None):
+    """accumulate: as for conv_bwd_data_raw"""
+    N, H, W, C = in_shape
+    assert w.dtype == f32 and dy.is_contiguous() and w.numel() == C * k * k
+    assert tuple(dy.shape) == (N,) + _dw_out_hw(H, W, stride) + (C,), "dy does not have the output's shape"
+    dx = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
+    if accumulate is not None:
+        assert tuple(accumulate.shape) == (N, H, W, C), "accumulate must have the input's shape"
+        accumulate = accumulate.to(dy.dtype).contiguous()
+    _lib.call("cr_dwconv_bwd_data", dy, w, dx, N, H, W, C, k, stride, _af(dy), accumulate)
+    return dx
+
+
+def dwconv_wgrad_ws_floats(M, C, k):
+    """workspace of cr_dwconv_bwd_weight (include/cr3dod.h): splits * C * k * k floats for M output pixels"""
+    return dw_wgrad_splits(M) * C * k * k
+
+
+def dwconv_bwd_weight_raw(dy, x, k, stride, sink=None):
+    """dW (C, k, k) f32, or added into `sink` (C * k * k floats) when given"""
+    N, H, W, C = x.shape
+    assert dy.dtype == x.dtype and dy.is_contiguous() and x.is_contiguous()
+    assert tuple(dy.shape) == (N,) + _dw_out_hw(H, W, stride) + (C,), "dy does not have the output's shape"
+    assert sink is None or (sink.dtype == f32 and sink.numel() == C * k * k)
+    n_ws = dwconv_wgrad_ws_floats(dy.shape[0] * dy.shape[1] * dy.shape[2], C, k)
+    ws = torch.empty((n_ws,), dtype=f32, device=x.device)
+    dw = sink if sink is not None else torch.empty((C, k, k), dtype=f32, device=x.device)
+    _lib.call("cr_dwconv_bwd_weight", dy, x, dw, N, H, W, C, k, stride, int(sink is not None), _af(x), ws, n_ws)
+    return None if sink is not None else dw
+
+
+def bn_needs_anyc(C):
+    """whether a BatchNorm over C channels is beyond cr_bn_bwd / cr_bn_bwd_mask (256 % (C / 8) == 0) -> cr_bn_bwd_anyc"""
+    return C % 8 != 0 or 256 % (C >> 3) != 0
+
+
+def bn_bwd_anyc_raw(dy, out, x, mean_invstd, gamma, beta, relu, dgamma, dbeta):
+    """-> dx; dgamma / dbeta (f32 [C]) are accumulated.  out None with relu: the mask is recomputed from x"""
+    C = x.shape[-1]
+    M = x.numel() // C
+    assert dy.dtype == x.dtype and dy.is_contiguous() and x.is_contiguous() and dy.shape == x.shape
+    assert out is None or (out.dtype == x.dtype and out.is_contiguous() and out.shape == x.shape)
+    assert dgamma.dtype == f32 and dbeta.dtype == f32 and dgamma.numel() == C == dbeta.numel()
+    ws = torch.empty((256, 2, C), dtype=f32, device=x.device)
+    dx = torch.empty_like(x)
+    _lib.call("cr_bn_bwd_anyc", dy, out, x, mean_invstd, gamma, beta, ws, dx, dgamma, dbeta, M, C, int(relu), _af(x))
+    return dx
+
+
+def colsum_wide_raw(x, out):
+    """out[c] += sum over all leading dimensions of x[..., c]; out f32 [C]"""
+    C = x.shape[-1]
+    assert x.is_contiguous() and out.dtype == f32 and out.numel() == C
+    ws = torch.empty((256, C), dtype=f32, device=x.device)
+    _lib.call("cr_colsum_wide", x, x.numel() // C, C, ws, out, _af(x))
+
+
+class _DwBNAct(torch.autograd.Function):
+    """depthwise k x k convolution + BatchNorm2d (+ ReLU), the structure of _DwBN -- train mode: statistics rows from the
+    convolution, cr_bn_fwd with its ReLU flag, cr_bn_bwd_anyc with the mask from the raw convolution output; frozen
+    statistics: the BatchNorm folded into the k * k taps (cr_fold_bn on the (C, k * k) weight, made on every call from the live
+    parameters), the ReLU in the convolution's epilogue, its mask from the stored output and cr_bn_frozen_unfold in the
+    backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, running_mean, running_var, k, stride, relu, eps, momentum, training,
+                slot=(None, 0)):
+        ctx.slot = slot
+        C = x.shape[3]
+        dev = x.device
+        kk = k * k
+        if training:
+            _STATS_EPOCH[0] += 1
+            Ho, Wo = _dw_out_hw(x.shape[1], x.shape[2], stride)
+            M = x.shape[0] * Ho * Wo
+            nparts = (M + 63) // 64
+            stats = torch.empty((nparts, 2, C), dtype=f32, device=dev)
+            y_raw = dwconv_fwd_raw(x, weight.detach(), k, stride, stats=stats)
+            out = torch.empty_like(y_raw)
+            mi = torch.empty((2, C), dtype=f32, device=dev)
+            _lib.call("cr_bn_fwd", y_raw, stats, nparts, gamma.detach(), beta.detach(), None, out, M, C, int(relu), float(eps),
+                      float(momentum), mi, running_mean, running_var, _af(x))
+            keep = None
+        else:
+            wf32 = torch.empty((C, kk), dtype=f32, device=dev)
+            bias_f = torch.empty((C,), dtype=f32, device=dev)
+            _lib.call("cr_fold_bn", weight.detach(), gamma.detach(), beta.detach(), running_mean, running_var, float(eps), wf32,
+                      bias_f, C, kk, 1)
+            out = dwconv_fwd_raw(x, wf32, k, stride, bias=bias_f, relu=relu)
+            y_raw, mi = wf32, None
+            keep = out if relu else None
+            ctx.frozen = (running_mean, running_var, float(eps))
+        ctx.cfg = (k, stride, relu, training)
+        ctx.beta_ref = beta
+        ctx.save_for_backward(x, weight, gamma, y_raw, mi, keep)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, weight, gamma, y_raw, mi, out = ctx.saved_tensors
+        k, stride, relu, training = ctx.cfg
+        C = x.shape[3]
+        dev = x.device
+        dout = dout.to(x.dtype).contiguous()
+        gs, bs = grad_sink(gamma), grad_sink(ctx.beta_ref)
+        if gs is not None and bs is not None:
+            dgamma, dbeta, ret_g, ret_b = gs, bs, None, None
+        else:
+            dgamma = torch.zeros((C,), dtype=f32, device=dev)
+            dbeta = torch.zeros((C,), dtype=f32, device=dev)
+            ret_g, ret_b = dgamma, dbeta
+        need_dw = ctx.needs_input_grad[1]
+        wsink = grad_sink(weight) if need_dw else None
+        dw = None
+        if training:
+            g = bn_bwd_anyc_raw(dout, None, y_raw, mi, gamma.detach(), ctx.beta_ref.detach(), relu, dgamma, dbeta)
+            w_bwd = weight.detach()
+            if need_dw:
+                dw = dwconv_bwd_weight_raw(g, x, k, stride, wsink)
+        else:
+            running_mean, running_var, eps = ctx.frozen
+            g = relu_bwd(out, dout) if relu else dout
+            w_bwd = y_raw                                   # the folded taps
+            sg = torch.zeros((C,), dtype=f32, device=dev)
+            colsum_wide_raw(g, sg)
+            dwf = dwconv_bwd_weight_raw(g, x, k, stride)
+            if need_dw and wsink is None:
+                dw = dwf                                    # scaled in place
+            dst = wsink if wsink is not None else dw
+            _lib.call("cr_bn_frozen_unfold", dwf, sg, weight.detach(), gamma.detach(), running_mean, running_var, eps, dst,
+                      int(wsink is not None), dgamma, dbeta, C, k * k)
+        dx = None
+        xslot, xi = ctx.slot
+        if ctx.needs_input_grad[0]:
+            if xslot is not None and xi > 1:                # not the first consumer of x: leave the contribution in the slot
+                _slot_put(xslot, dwconv_bwd_data_raw(g, w_bwd, x.shape, k, stride, accumulate=_slot_fold(xslot)))
+            else:
+                dx = dwconv_bwd_data_raw(g, w_bwd, x.shape, k, stride,
+                                         accumulate=_slot_take(xslot) if xslot is not None else None)
+        elif xslot is not None:
+            raise RuntimeError("gradient slot registered for an input that needs no gradient")
+        if dw is not None:
+            dw = dw.view(weight.shape)
+        return dx, dw, ret_g, ret_b, None, None, None, None, None, None, None, None, None
+
+
+def dwconv_bn_act(x, weight, gamma, beta, running_mean, running_var, k=3, stride=1, relu=True, eps=1e-5, momentum=0.1,
+                  training=True):
+    """relu?(BatchNorm(depthwise_conv k x k(x))), pad k // 2; weight: f32, C * k * k elements in (C, k, k) order (a (C,1,k,k)
+    parameter or a padded (C, k * k) compute copy)"""
+    _need_cuda(x, "conv input")
+    return _DwBNAct.apply(x, weight, gamma, beta, running_mean, running_var, int(k), int(stride), bool(relu), eps, momentum,
+                          bool(training), _slot_register(x, False))
 
 
 class _UpsampleAdd(torch.autograd.Function):

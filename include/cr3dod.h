@@ -556,6 +556,32 @@ typedef struct cr_pdesc {
 } cr_pdesc;
 int cr_padded_pack(cr_ctx* ctx, const void* descs_dev, int ndesc, float* base, float* baseT, int mode);
 
+/* ---- MNASNet trunk (3dod_amd/csrc/mnasnet.hip; the reference's cubercnn/modeling/backbone/mnasnet.py:13-38 takes
+ * torchvision's mnasnet1_0 [third-party]) --------------------------------------------------------------------------------
+ * Depthwise k x k convolution: nn.Conv2d(C, C, k, stride, padding=k/2, groups=C, bias=False), k in {3,5}.  The contract of
+ * cr_dwconv3x3_* with w f32 (C, k, k); k = 5 runs kernels of its own (4 channels per thread), bwd_data / bwd_weight of k = 3
+ * ARE cr_dwconv3x3_bwd_*.  fwd: relu in {0,1} clamps the output (after the bias) before it is stored and counted in stats.
+ * stride in {1,2}, C % 8 == 0, any N, H, W >= 1; anything else returns CR_EINVAL without a launch.
+ *   bwd_weight  ws must hold splits * C * k * k floats (ws_floats), splits = ceil(M / max(64, ceil(M/128))), M = N * Ho * Wo;
+ *               two passes, ranges added in index order: bit-identical from run to run. */
+int cr_dwconv_fwd(cr_ctx* ctx, const void* x, const float* w, void* y, int N, int H, int W, int C, int k, int stride,
+                  const float* bias, float* stats, int relu, int act_f32);
+int cr_dwconv_bwd_data(cr_ctx* ctx, const void* dy, const float* w, void* dx, int N, int H, int W, int C, int k, int stride,
+                       int act_f32, const void* accumulate);
+int cr_dwconv_bwd_weight(cr_ctx* ctx, const void* dy, const void* x, float* dw, int N, int H, int W, int C, int k, int stride,
+                         int accumulate, int act_f32, float* ws, int64_t ws_floats);
+/* BatchNorm backward for any C % 8 == 0, C <= 2048 (cr_bn_bwd / cr_bn_bwd_mask need 256 % (C / 8) == 0): the contract of
+ * cr_bn_bwd_mask without dres.  relu in {0,1}; with relu the mask is out > 0 when out is given and otherwise the sign of the
+ * value cr_bn_fwd stored, recomputed bit for bit from x, mean_invstd, gamma and beta.  dx is written, dgamma / dbeta are
+ * accumulated (+=).  ws: f32 workspace of at least 256 * 2 * C floats.  No atomics, every channel's sums are formed in a
+ * fixed order: bit-identical from run to run. */
+int cr_bn_bwd_anyc(cr_ctx* ctx, const void* dy, const void* out, const void* x, const float* mean_invstd, const float* gamma,
+                   const float* beta, float* ws, void* dx, float* dgamma, float* dbeta, int64_t M, int C, int relu,
+                   int act_f32);
+/* out[c] += sum_m x[m][c], x (M, C) bf16 or f32, C % 8 == 0: a thread adds its rows in float32, everything across threads is
+ * added in double in a fixed order (bit-identical from run to run).  ws: at least 256 * C floats. */
+int cr_colsum_wide(cr_ctx* ctx, const void* x, int64_t M, int C, float* ws, float* out, int act_f32);
+
 /* FC weights of the RoI heads (roi_heads.py:2160-2204, cube_head.py:152-202).  w f32 (O, C, HW) in the checkpoint's
  * (c,h,w) column order -> wb bf16 (O, HW, C) for NHWC-flattened inputs (HW = 1: plain cast); and the transpose for the
  * gradient: acc f32 (O, C, HW) += g bf16 (O, HW, C). */

@@ -145,6 +145,10 @@ SIGNATURES = {
     "cr_dwconv_bwd_weight": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int64],
     "cr_bn_bwd_anyc": [P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int, c_int, c_int],
     "cr_colsum_wide": [P, P, c_int64, c_int, P, P, c_int],
+    "cr_bn_pair_fwd": [P, P, P, P, P, c_int, P, P, P, P, P, c_int64, c_int, c_float, c_float, c_float, c_float, P, P, P, P, P, P,
+                       c_int],
+    "cr_bn_pair_bwd_blocks": [c_int64, c_int],
+    "cr_bn_pair_bwd": [P, P, P, P, P, P, P, P, P, P, c_int64, P, P, P, P, P, P, c_int64, c_int, c_int],
     "cr_cube_decode_infer": [P, P, c_int, P, c_int, P, P, P, P, P, c_int, c_int, P, c_int, c_int, P, P],
     "cr_cube_select_param": [P, P, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, c_int, c_int, P, P, P,
                              c_int, c_int, P, P],
@@ -204,6 +208,11 @@ def check(rc, what):
 def topk_blocks(n, k):
     """cr_topk_blocks: a host-side count, no context and no status"""
     return load().cr_topk_blocks(n, k)
+
+
+def bn_pair_bwd_blocks(M, C):
+    """cr_bn_pair_bwd_blocks: a host-side count, no context and no status"""
+    return load().cr_bn_pair_bwd_blocks(M, C)
 
 
 # ---- per-device context bound to torch's current stream ---------------------

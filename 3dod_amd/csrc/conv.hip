@@ -27,6 +27,7 @@
 // e of every lane's A and B fragments, i.e. the k set {e, 4+e, 8+e, 12+e} -- the same permutation on both operands.
 #include "cr_common.h"
 #include "cr_elem.h"
+#include "bn_finalize.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -3503,47 +3504,13 @@ extern "C" int cr_fc_grad_accum(cr_ctx* ctx, const void* g, float* acc, int O, i
 // ---------------------------------------------------------------------------
 // BatchNorm2d (training mode, per-GPU statistics: dla.py:17 BatchNorm = nn.BatchNorm2d)
 // ---------------------------------------------------------------------------
-// finalize: per-tile partials [nparts][2][C] -> mean / invstd (+ running stats update, momentum, unbiased var).
-// One workgroup per channel; strided serial sums + a fixed-order LDS tree, in double: reproducible and accurate
-// (no E[x^2]-E[x]^2 cancellation at float precision).
-// bn_finalize_tail: the 256 lane sums (s, q) of channel c -> the 128 -> 1 tree and the final arithmetic (the whole block calls it)
-__device__ __forceinline__ void bn_finalize_tail(double s, double q, int c, int C, float count, float eps, float momentum,
-                                                 float* __restrict__ mean_invstd, float* __restrict__ running_mean,
-                                                 float* __restrict__ running_var) {
-    __shared__ double ss[256], sq[256];
-    const int t = threadIdx.x;
-    ss[t] = s; sq[t] = q;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (t < off) { ss[t] += ss[t + off]; sq[t] += sq[t + off]; }
-        __syncthreads();
-    }
-    if (t == 0) {
-        // the fused multiply-adds are the ones the compiler formed from the plain expressions, now written out (the order is
-        // part of what tests/test_gpu_bn_finalize_order.py specifies)
-#pragma clang fp contract(off)
-        const double mean = ss[0] / (double)count;
-        double var = __builtin_fma(-mean, mean, sq[0] / (double)count);
-        if (var < 0.0) var = 0.0;
-        mean_invstd[c] = (float)mean;
-        mean_invstd[C + c] = (float)(1.0 / sqrt(var + (double)eps));
-        if (running_mean) {
-            const double unbiased = count > 1.f ? var * (double)count / ((double)count - 1.0) : var;
-            running_mean[c] = (float)__builtin_fma((double)momentum, mean, (1.0 - momentum) * running_mean[c]);
-            running_var[c] = (float)__builtin_fma((double)momentum, unbiased, (1.0 - momentum) * running_var[c]);
-        }
-    }
-}
-
+// The finalisation arithmetic lives in bn_finalize.h: cr_bn_pair_fwd (csrc/resnet.hip) runs the same code.
 __global__ __launch_bounds__(256) void k_bn_finalize(const float* __restrict__ stats, int nparts, int C, float count,
                                                      float eps, float momentum, float* __restrict__ mean_invstd,
                                                      float* __restrict__ running_mean, float* __restrict__ running_var) {
     const int c = blockIdx.x, t = threadIdx.x;
-    double s = 0.0, q = 0.0;
-    for (int r = t; r < nparts; r += 256) {
-        s += (double)stats[(size_t)r * 2 * C + c];
-        q += (double)stats[(size_t)r * 2 * C + C + c];
-    }
+    double s, q;
+    bn_strided_row_sums(stats, nparts, C, c, t, s, q);
     bn_finalize_tail(s, q, c, C, count, eps, momentum, mean_invstd, running_mean, running_var);
 }
 
@@ -3552,25 +3519,10 @@ __global__ __launch_bounds__(256) void k_bn_finalize(const float* __restrict__ s
 // step 1 reads every row once: thread (row lane t of 256, column j of 2C) adds rows t, t + 256, ... ascending in double --
 // the sum thread t of k_bn_finalize forms for that column, bit for bit -- into lanes[t][j]; consecutive threads take
 // consecutive columns, so a wave reads whole rows.  Step 2 runs the tree and the arithmetic of the tail over those 256 doubles.
-static constexpr int BN_LANE_BATCH = 8;     // loads in flight per thread in step 1 (the additions stay in row order)
 __global__ __launch_bounds__(256) void k_bn_stats_lanes(const float* __restrict__ stats, int nparts, int C2,
                                                         double* __restrict__ lanes) {
     const int f = blockIdx.x * 256 + threadIdx.x;         // < 256 * C2 (grid = C2 blocks)
-    const int t = f / C2, j = f - t * C2;
-    const float* p = stats + (size_t)t * C2 + j;
-    const size_t step = (size_t)256 * C2;
-    double s = 0.0;
-    int r = t;
-    for (; r + 256 * (BN_LANE_BATCH - 1) < nparts; r += 256 * BN_LANE_BATCH) {
-        float v[BN_LANE_BATCH];
-#pragma unroll
-        for (int u = 0; u < BN_LANE_BATCH; ++u) v[u] = p[(size_t)u * step];
-#pragma unroll
-        for (int u = 0; u < BN_LANE_BATCH; ++u) s += (double)v[u];
-        p += BN_LANE_BATCH * step;
-    }
-    for (; r < nparts; r += 256) { s += (double)*p; p += step; }
-    lanes[f] = s;
+    lanes[f] = bn_lane_column_sum(stats, nparts, C2, f);
 }
 
 __global__ __launch_bounds__(256) void k_bn_finalize_lanes(const double* __restrict__ lanes, int C, float count, float eps,
@@ -3581,14 +3533,7 @@ __global__ __launch_bounds__(256) void k_bn_finalize_lanes(const double* __restr
                      running_mean, running_var);
 }
 
-// The forward's value before the residual and the ReLU, in the one form every kernel below uses: subtract, multiply, then ONE
-// fused multiply-add (what the compiler made of the plain expression, now pinned).  The backward of a ReLU layer without a
-// residual recomputes it from x to get the ReLU mask instead of reading the forward's output, so the bits must agree.
-__device__ __forceinline__ float bn_affine(float x, float mean, float invstd, float gamma, float beta) {
-#pragma clang fp contract(off)
-    const float xh = (x - mean) * invstd;
-    return __builtin_fmaf(xh, gamma, beta);
-}
+// bn_affine (bn_finalize.h): the forward's value before the residual and the ReLU, in the one form every kernel below uses.
 // whether the forward STORED a positive value for the pre-activation v (no residual): the ReLU, then the rounding of the store
 template <typename T> __device__ __forceinline__ bool bn_relu_on(float v);
 template <> __device__ __forceinline__ bool bn_relu_on<float>(float v) { return fmaxf(v, 0.f) > 0.f; }
@@ -3631,37 +3576,10 @@ __global__ __launch_bounds__(256) void k_bn_apply_fused(const T* __restrict__ x,
                                                         int px_per_block) {
     __shared__ double sd[2][8][32];
     __shared__ float sc[2][32];                          // mean, invstd of this slice
-    const int t = threadIdx.x, ch = t & 31, rl = t >> 5;
-    const int cbase = blockIdx.y * 32, c = cbase + ch;
-    {
-        double s = 0.0, q = 0.0;
-        for (int r = rl; r < nparts; r += 8) {
-            s += (double)stats[(size_t)r * 2 * C + c];
-            q += (double)stats[(size_t)r * 2 * C + C + c];
-        }
-        sd[0][rl][ch] = s; sd[1][rl][ch] = q;
-    }
-    __syncthreads();
-    if (t < 32) {
-        double s = 0.0, q = 0.0;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) { s += sd[0][r][t]; q += sd[1][r][t]; }
-        const double mean = s / (double)count;
-        double var = q / (double)count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float mf = (float)mean, isf = (float)(1.0 / sqrt(var + (double)eps));
-        sc[0][t] = mf;
-        sc[1][t] = isf;
-        if (blockIdx.x == 0) {
-            mean_invstd[cbase + t] = mf;
-            mean_invstd[C + cbase + t] = isf;
-            if (running_mean) {
-                const double unbiased = count > 1.f ? var * (double)count / ((double)count - 1.0) : var;
-                running_mean[cbase + t] = (float)((1.0 - momentum) * running_mean[cbase + t] + momentum * mean);
-                running_var[cbase + t] = (float)((1.0 - momentum) * running_var[cbase + t] + momentum * unbiased);
-            }
-        }
-    }
+    const int t = threadIdx.x;
+    const int cbase = blockIdx.y * 32;
+    bn_slice_finalize(stats, nparts, C, cbase, count, eps, momentum, blockIdx.x == 0, mean_invstd, running_mean, running_var, sd,
+                      sc);
     __syncthreads();
     const int cgl = t & 3;                               // 8-channel group inside the slice
     float mu[8], is8[8], ga[8], be[8];
@@ -3686,10 +3604,7 @@ __global__ __launch_bounds__(256) void k_bn_apply_fused(const T* __restrict__ x,
     }
 }
 
-// at most this many statistics rows take the fused finalize + apply (k_bn_apply_fused): the 64x64 and smaller maps
-static constexpr int BN_FUSE_ROWS = 256;
-// from this many statistics rows on the unfused finalize runs as k_bn_stats_lanes + k_bn_finalize_lanes
-static constexpr int BN_LANES_MIN_ROWS = 2048;
+// BN_FUSE_ROWS / BN_LANES_MIN_ROWS (bn_finalize.h): the row counts at which the route changes
 
 extern "C" int cr_bn_fwd(cr_ctx* ctx, const void* x, const float* stats, int nparts, const float* gamma,
                          const float* beta, const void* residual, void* y, int64_t M, int C, int relu, float eps,

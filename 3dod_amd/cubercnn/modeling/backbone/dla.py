@@ -17,11 +17,13 @@ from .fpn import FPN, Backbone, to_channels_last
 BatchNorm = nn.BatchNorm2d
 
 
-def _conv_bn(x, conv, bn, relu, residual=None):
+def _conv_bn(x, conv, bn, relu, residual=None, wide_sums=False):
     w = conv.weight
     if conv.groups == 1 and w.shape[1] < x.shape[-1]:      # RGB stem: activations carry 8 (bf16) or 4 (f32) channels, 3 real + zeros
         w = ops.pad_input_channels(w, x.shape[-1])
     grouped = {"groups": conv.groups} if conv.groups > 1 else {}         # dense layers: the call as it always was
+    if wide_sums:                                         # ops.conv_bn_act: the backward's per-channel sums are added in double
+        grouped["wide_sums"] = True
     return ops.conv_bn_act(x, w, bn.weight, bn.bias, bn.running_mean, bn.running_var, stride=conv.stride[0],
                            pad=conv.padding[0], relu=relu, residual=residual, eps=bn.eps, momentum=bn.momentum,
                            training=bn.training, **grouped)

@@ -786,8 +786,9 @@ def conv_bn_folded(x, weight, gamma, beta, running_mean, running_var, stride=1, 
 
 
 def conv_bn_act(x, weight, gamma, beta, running_mean, running_var, stride=1, pad=0, relu=True, residual=None,
-                eps=1e-5, momentum=0.1, training=True, groups=1):
-    """groups > 1: the grouped 3x3 kernels (cr_conv2d_grouped_*; pad 1, Cin == Cout) in every route below"""
+                eps=1e-5, momentum=0.1, training=True, groups=1, wide_sums=False):
+    """groups > 1: the grouped 3x3 kernels (cr_conv2d_grouped_*; pad 1, Cin == Cout) in every route below.  wide_sums: as in
+    conv_bn_act_live (the backward's per-channel sums are added across threads in double)"""
     if not training and not (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or gamma.requires_grad
                                                           or (residual is not None and residual.requires_grad))):
         return conv_bn_folded(x, weight, gamma, beta, running_mean, running_var, stride, pad, relu, residual, eps, groups)
@@ -796,7 +797,126 @@ def conv_bn_act(x, weight, gamma, beta, running_mean, running_var, stride=1, pad
     xs = _slot_register(x, True)
     rs = _slot_register(residual, False) if residual is not None else (None, 0)
     return _ConvBN.apply(x, as_krsc(weight), gamma, beta, residual, running_mean, running_var, stride, pad, relu, eps,
-                         momentum, training, (xs, rs), groups)
+                         momentum, training, (xs, rs), groups, bool(wide_sums))
+
+
+# --------------------------------------------------------------------------
+# two convolutions, each with its own BatchNorm(train), added, ReLU: the projection-shortcut tail of a ResNet Bottleneck
+# (csrc/resnet.hip).  out = relu(bn_a(conv_a(xa)) + bn_b(conv_b(xb)))
+# --------------------------------------------------------------------------
+def bn_pair_bwd_ws_floats(M, C):
+    """floats of workspace cr_bn_pair_bwd needs (include/cr3dod.h); outside its domain the library refuses the call itself"""
+    return (_lib.bn_pair_bwd_blocks(M, C) + 1) * 3 * C
+
+
+def bn_pair_fwd_raw(ya, yb, stats_a, stats_b, bn_a, bn_b):
+    """bn_*: (gamma, beta, running_mean, running_var, eps, momentum) -> out, mean_invstd_a, mean_invstd_b"""
+    C = ya.shape[-1]
+    M = ya.numel() // C
+    out = torch.empty_like(ya)
+    mia = torch.empty((2, C), dtype=f32, device=ya.device)
+    mib = torch.empty((2, C), dtype=f32, device=ya.device)
+    _lib.call("cr_bn_pair_fwd", ya, yb, stats_a, stats_b, stats_a.shape[0], bn_a[0], bn_a[1], bn_b[0], bn_b[1], out, M, C,
+              float(bn_a[4]), float(bn_a[5]), float(bn_b[4]), float(bn_b[5]), mia, mib, bn_a[2], bn_a[3], bn_b[2], bn_b[3],
+              _af(ya))
+    return out, mia, mib
+
+
+def bn_pair_bwd_raw(dout, out, ya, yb, mia, mib, gamma_a, gamma_b, dgamma_a, dbeta_a, dgamma_b, dbeta_b):
+    """-> dxa_raw, dxb_raw; the four parameter gradients are accumulated into"""
+    C = ya.shape[-1]
+    M = ya.numel() // C
+    n = bn_pair_bwd_ws_floats(M, C)
+    ws = torch.empty((n,), dtype=f32, device=ya.device)
+    dxa, dxb = torch.empty_like(ya), torch.empty_like(yb)
+    _lib.call("cr_bn_pair_bwd", dout, out, ya, yb, mia, mib, gamma_a, gamma_b, ws, n, dxa, dxb, dgamma_a, dbeta_a, dgamma_b,
+              dbeta_b, M, C, _af(ya))
+    return dxa, dxb
+
+
+class _ConvBNPair(torch.autograd.Function):
+    """side a: (xa, wa, gamma_a, beta_a), side b: (xb, wb, gamma_b, beta_b); bufs: the four running-statistics buffers;
+    cfg: (stride_a, pad_a, eps_a, momentum_a, stride_b, pad_b, eps_b, momentum_b); slots: the gradient slots of xa and xb"""
+
+    @staticmethod
+    def forward(ctx, xa, wa, gamma_a, beta_a, xb, wb, gamma_b, beta_b, bufs, cfg, slots):
+        sa, pa, eps_a, mom_a, sb, pb, eps_b, mom_b = cfg
+        C = wa.shape[0]
+        assert wb.shape[0] == C and xa.dtype == xb.dtype
+        wpa, _ = prepared_weights(wa, xa.requires_grad, xa.dtype)
+        wpb, _ = prepared_weights(wb, xb.requires_grad, xb.dtype)
+        _STATS_EPOCH[0] += 1
+        ka, kb = wa.shape[2], wb.shape[2]
+        N_, H_, W_, _ = xa.shape
+        M = N_ * ((H_ + 2 * pa - ka) // sa + 1) * ((W_ + 2 * pa - ka) // sa + 1)
+        nparts = (M + 63) // 64                # statistics rows are per 64 pixels
+        stats_a = torch.empty((nparts, 2, C), dtype=f32, device=xa.device)
+        stats_b = torch.empty((nparts, 2, C), dtype=f32, device=xa.device)
+        ya = conv_fwd_raw(xa, wpa, C, ka, sa, pa, stats=stats_a)
+        yb = conv_fwd_raw(xb, wpb, C, kb, sb, pb, stats=stats_b)
+        if ya.shape != yb.shape:
+            raise _lib.CrError(f"conv_bn_pair_act: the two convolutions give {tuple(ya.shape)} and {tuple(yb.shape)}")
+        out, mia, mib = bn_pair_fwd_raw(ya, yb, stats_a, stats_b,
+                                        (gamma_a.detach(), beta_a.detach(), bufs[0], bufs[1], eps_a, mom_a),
+                                        (gamma_b.detach(), beta_b.detach(), bufs[2], bufs[3], eps_b, mom_b))
+        ctx.cfg, ctx.slots = cfg, slots
+        ctx.beta_refs = (beta_a, beta_b)
+        ctx.save_for_backward(xa, wa, gamma_a, xb, wb, gamma_b, ya, yb, out, mia, mib)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        xa, wa, gamma_a, xb, wb, gamma_b, ya, yb, out, mia, mib = ctx.saved_tensors
+        sa, pa, _, _, sb, pb, _, _ = ctx.cfg
+        C = wa.shape[0]
+        dout = dout.to(ya.dtype).contiguous()
+        acc, ret = [], []
+        for gamma, beta in ((gamma_a, ctx.beta_refs[0]), (gamma_b, ctx.beta_refs[1])):
+            gs, bs = grad_sink(gamma), grad_sink(beta)
+            if gs is not None and bs is not None:
+                acc += [gs, bs]
+                ret += [None, None]
+            else:
+                fresh = [torch.zeros((C,), dtype=f32, device=ya.device) for _ in range(2)]
+                acc += fresh
+                ret += fresh
+        dxa_raw, dxb_raw = bn_pair_bwd_raw(dout, out, ya, yb, mia, mib, gamma_a.detach(), gamma_b.detach(), *acc)
+        grads = []
+        sides = ((xa, wa, dxa_raw, sa, pa, ctx.slots[0], 0), (xb, wb, dxb_raw, sb, pb, ctx.slots[1], 4))
+        for x, w, dx_raw, stride, pad, (xslot, xi), at in sides:
+            k = w.shape[2]
+            dx = None
+            if ctx.needs_input_grad[at]:
+                _, wt = prepared_weights(w, True, x.dtype)
+                bwd_data = lambda a: conv_bwd_data_raw(dx_raw, wt, x.shape, k, stride, pad, accumulate=a)
+                if xslot is not None and xi > 1:            # not the first consumer of x: leave the contribution in the slot
+                    _slot_put(xslot, bwd_data(_slot_fold(xslot)))
+                else:
+                    dx = bwd_data(_slot_take(xslot) if xslot is not None else None)
+            elif xslot is not None:
+                raise RuntimeError("gradient slot registered for an input that needs no gradient")
+            dw = conv_bwd_weight_raw(dx_raw, x, k, stride, pad, grad_sink(w)) if ctx.needs_input_grad[at + 1] else None
+            grads.append((dx, dw))
+        return (grads[0][0], grads[0][1], ret[0], ret[1], grads[1][0], grads[1][1], ret[2], ret[3], None, None, None)
+
+
+def conv_bn_pair_act(xa, weight_a, bn_a, xb, weight_b, bn_b, stride_a=1, pad_a=0, stride_b=1, pad_b=0):
+    """relu(bn_a(conv(xa, weight_a)) + bn_b(conv(xb, weight_b))); bn_*: (gamma, beta, running_mean, running_var, eps, momentum,
+    training).  Both BatchNorms in training mode: two convolutions with statistics rows, then cr_bn_pair_fwd -- the normalised
+    shortcut is never materialised; the backward is cr_bn_pair_bwd and the convolutions' own backward kernels.  Frozen
+    statistics (with or without gradients) take the folded routes of conv_bn_act: one convolution per BatchNorm with bias,
+    residual and ReLU in its epilogue.  Their backward forms the bias gradients -- plain sums of the masked cotangent over the
+    pixels -- with cr_colsum_wide (wide_sums): the weight gradient's own bias sum adds a block's rows one after the other in
+    float32, which measured 2.5 .. 3.1 x the float32 restatement's error on bn3.bias."""
+    if not (bn_a[6] and bn_b[6]):
+        identity = conv_bn_act(xb, weight_b, bn_b[0], bn_b[1], bn_b[2], bn_b[3], stride_b, pad_b, False, None, bn_b[4], bn_b[5],
+                               bn_b[6], wide_sums=not bn_b[6])
+        return conv_bn_act(xa, weight_a, bn_a[0], bn_a[1], bn_a[2], bn_a[3], stride_a, pad_a, True, identity, bn_a[4], bn_a[5],
+                           bn_a[6], wide_sums=not bn_a[6])
+    slots = (_slot_register(xa, True), _slot_register(xb, True))
+    return _ConvBNPair.apply(xa, as_krsc(weight_a), bn_a[0], bn_a[1], xb, as_krsc(weight_b), bn_b[0], bn_b[1],
+                             (bn_a[2], bn_a[3], bn_b[2], bn_b[3]),
+                             (stride_a, pad_a, bn_a[4], bn_a[5], stride_b, pad_b, bn_b[4], bn_b[5]), slots)
 
 
 # --------------------------------------------------------------------------

@@ -582,6 +582,31 @@ int cr_bn_bwd_anyc(cr_ctx* ctx, const void* dy, const void* out, const void* x, 
  * added in double in a fixed order (bit-identical from run to run).  ws: at least 256 * C floats. */
 int cr_colsum_wide(cr_ctx* ctx, const void* x, int64_t M, int C, float* ws, float* out, int act_f32);
 
+/* ResNet-50/101 trunk (csrc/resnet.hip): the projection-shortcut tail of a Bottleneck block with two training-mode BatchNorms,
+ *   out = relu( bn_a(ya) + bn_b(yb) ),   ya, yb raw convolution outputs (M, C) bf16 or f32 (act_f32), NHWC,
+ * in the channel domain of cr_bn_bwd: C % 8 == 0, C <= 2048, 256 % (C / 8) == 0; any M >= 1.  Anything else returns CR_EINVAL
+ * without a launch.  No atomics, every sum in a fixed order: bit-identical from run to run.
+ *   fwd  stats_a / stats_b: the convolution epilogues' rows (nparts, 2, C), nparts = ceil(M / 64).  Each BatchNorm is finalised
+ *        by the code of cr_bn_fwd (the same three routes by nparts), so mean_invstd_* (2, C) and the running statistics (may
+ *        be NULL, in pairs) get the bits cr_bn_fwd gives; in f32, out has the bits of
+ *        cr_bn_fwd(yb, no relu) -> cr_bn_fwd(ya, residual = that, relu).  In bf16 the shortcut is not rounded in between.
+ *   bwd  g = dout * [out > 0]: dxa_raw / dxb_raw = the BatchNorm input gradients; dgamma_* / dbeta_* are accumulated (+=; the
+ *        two BatchNorms' buffers must differ).  A thread adds its rows (8 while the grid has workgroups left) in float32,
+ *        everything across threads and workgroups is added in double.  dout, out, ya, yb are read twice each.
+ *        ws: ws_floats >= (cr_bn_pair_bwd_blocks(M, C) + 1) * 3 * C floats (a host-side count, no context and no status; 0
+ *        outside the domain).
+ *   fwd  also refuses a mean_invstd or running-statistics buffer that is shared between the two BatchNorms. */
+int cr_bn_pair_fwd(cr_ctx* ctx, const void* ya, const void* yb, const float* stats_a, const float* stats_b, int nparts,
+                   const float* gamma_a, const float* beta_a, const float* gamma_b, const float* beta_b, void* out, int64_t M,
+                   int C, float eps_a, float momentum_a, float eps_b, float momentum_b, float* mean_invstd_a,
+                   float* mean_invstd_b, float* running_mean_a, float* running_var_a, float* running_mean_b,
+                   float* running_var_b, int act_f32);
+int cr_bn_pair_bwd_blocks(int64_t M, int C);
+int cr_bn_pair_bwd(cr_ctx* ctx, const void* dout, const void* out, const void* ya, const void* yb, const float* mean_invstd_a,
+                   const float* mean_invstd_b, const float* gamma_a, const float* gamma_b, float* ws, int64_t ws_floats,
+                   void* dxa_raw, void* dxb_raw, float* dgamma_a, float* dbeta_a, float* dgamma_b, float* dbeta_b, int64_t M,
+                   int C, int act_f32);
+
 /* FC weights of the RoI heads (roi_heads.py:2160-2204, cube_head.py:152-202).  w f32 (O, C, HW) in the checkpoint's
  * (c,h,w) column order -> wb bf16 (O, HW, C) for NHWC-flattened inputs (HW = 1: plain cast); and the transpose for the
  * gradient: acc f32 (O, C, HW) += g bf16 (O, HW, C). */

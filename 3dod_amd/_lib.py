@@ -149,6 +149,9 @@ SIGNATURES = {
                        c_int],
     "cr_bn_pair_bwd_blocks": [c_int64, c_int],
     "cr_bn_pair_bwd": [P, P, P, P, P, P, P, P, P, P, c_int64, P, P, P, P, P, P, c_int64, c_int, c_int],
+    "cr_groupnorm_ws_floats": [c_int64, c_int64, c_int],
+    "cr_groupnorm_fwd": [P, P, P, P, P, P, P, P, c_int64, c_int, c_int64, c_int, c_int, c_float, c_int, c_int],
+    "cr_groupnorm_bwd": [P, P, P, P, P, P, P, c_int64, P, P, P, c_int, c_int64, c_int, c_int, c_int, c_int],
     "cr_cube_decode_infer": [P, P, c_int, P, c_int, P, P, P, P, P, c_int, c_int, P, c_int, c_int, P, P],
     "cr_cube_select_param": [P, P, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, c_int, c_int, P, P, P,
                              c_int, c_int, P, P],
@@ -213,6 +216,11 @@ def topk_blocks(n, k):
 def bn_pair_bwd_blocks(M, C):
     """cr_bn_pair_bwd_blocks: a host-side count, no context and no status"""
     return load().cr_bn_pair_bwd_blocks(M, C)
+
+
+def groupnorm_ws_floats(N, HW, C):
+    """cr_groupnorm_ws_floats: a host-side count, no context and no status"""
+    return load().cr_groupnorm_ws_floats(N, HW, C)
 
 
 # ---- per-device context bound to torch's current stream ---------------------

@@ -51,22 +51,32 @@ class LastLevelMaxPool(nn.Module):
         return [ops.subsample2x(x)]
 
 
+FPN_NORMS = ("", "GN")
+
+
 class FPN(Backbone):
-    """lateral 1x1 + top-down nearest-2x sum + output 3x3, no norm; optional top block (LastLevelMaxPool)."""
+    """lateral 1x1 + top-down nearest-2x sum + output 3x3; optional top block (LastLevelMaxPool).  norm "" (the reference's
+    configuration: convolutions with bias) or "GN" (detectron2's get_norm("GN") [third-party, restated]: bias-free
+    convolutions, each followed by its own torch.nn.GroupNorm(32, out_channels) registered as `.norm`, no activation)."""
 
     def __init__(self, bottom_up, in_features, out_channels, norm="", top_block=None, fuse_type="sum"):
         super().__init__()
-        assert norm == "", "only the configuration used by the reference is built"
+        if norm not in FPN_NORMS:
+            raise ValueError('built: MODEL.FPN.NORM "" / "GN"; got NORM "{}"'.format(norm))
         assert fuse_type in ("sum", "avg")
+        use_bias = norm == ""
         input_shapes = bottom_up.output_shape()
         strides = [input_shapes[f].stride for f in in_features]
         in_channels_per_feature = [input_shapes[f].channels for f in in_features]
         lateral_convs, output_convs = [], []
         for idx, in_channels in enumerate(in_channels_per_feature):
-            lateral_conv = nn.Conv2d(in_channels, out_channels, kernel_size=1, bias=True)
-            output_conv = nn.Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=True)
+            lateral_conv = nn.Conv2d(in_channels, out_channels, kernel_size=1, bias=use_bias)
+            output_conv = nn.Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=use_bias)
             c2_xavier_fill(lateral_conv)
             c2_xavier_fill(output_conv)
+            if norm == "GN":                         # (weight 1, bias 0)
+                lateral_conv.norm = nn.GroupNorm(32, out_channels)
+                output_conv.norm = nn.GroupNorm(32, out_channels)
             stage = int(math.log2(strides[idx]))
             self.add_module("fpn_lateral{}".format(stage), lateral_conv)
             self.add_module("fpn_output{}".format(stage), output_conv)
@@ -88,6 +98,7 @@ class FPN(Backbone):
         self._out_feature_channels = {k: out_channels for k in self._out_features}
         self._size_divisibility = strides[-1]
         self._fuse_type = fuse_type
+        self._norm = norm
         to_channels_last(self)
 
     @property
@@ -104,21 +115,28 @@ class FPN(Backbone):
         # top-down pathway first (lateral 1x1 + nearest-2x sum, coarse to fine), then ALL output convolutions in one grouped
         # launch per direction (ops.conv_bias_act_group): they are independent of each other, and alone the coarse levels
         # are a handful of tiles each
-        lat0 = self.lateral_convs[0]
         # a trunk whose maps carry pad channels (ShuffleNetV2) supplies lateral weights with zero columns at the pads
         lw = self.bottom_up.lateral_weights() if hasattr(self.bottom_up, "lateral_weights") else None
         lat_w = (lambda i: self.lateral_convs[i].weight) if lw is None else (lambda i: lw[self.in_features[-i - 1]])
-        prev = ops.conv_bias_act(bottom_up_features[self.in_features[-1]], lat_w(0), lat0.bias, 1, 0)
+        if self._norm == "GN":
+            # conv -> GroupNorm on every lateral (before the top-down add) and on every output convolution's result
+            gn = lambda m: (m.norm.weight, m.norm.bias, m.norm.num_groups, m.norm.eps)
+            lateral_of = lambda idx, feats: ops.conv_gn_act(feats, lat_w(idx), gn(self.lateral_convs[idx]), 1, 0)
+        else:
+            lateral_of = lambda idx, feats: ops.conv_bias_act(feats, lat_w(idx), self.lateral_convs[idx].bias, 1, 0)
+        prev = lateral_of(0, bottom_up_features[self.in_features[-1]])
         inner = [prev]
         for idx, lateral_conv in enumerate(self.lateral_convs):
             if idx > 0:
                 features = bottom_up_features[self.in_features[-idx - 1]]
-                lateral = ops.conv_bias_act(features, lat_w(idx), lateral_conv.bias, 1, 0)
+                lateral = lateral_of(idx, features)
                 prev = ops.upsample2x_add(lateral, prev)
                 if self._fuse_type == "avg":
                     prev = prev / 2
                 inner.append(prev)
         outs = ops.conv_bias_act_group(inner, [c.weight for c in self.output_convs], [c.bias for c in self.output_convs], pad=1)
+        if self._norm == "GN":                                 # the grouped launch takes the missing bias; one GroupNorm per level
+            outs = [ops.group_norm(o, *gn(c)) for o, c in zip(outs, self.output_convs)]
         results = outs[::-1]                                   # fine -> coarse
         if self.top_block is not None:
             src = bottom_up_features[self.top_block.in_feature] if self.top_block.in_feature in bottom_up_features \

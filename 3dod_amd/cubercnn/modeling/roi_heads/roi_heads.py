@@ -17,7 +17,7 @@ from ....d2lite import (ROI_HEADS_REGISTRY, ROI_BOX_HEAD_REGISTRY, Boxes, Instan
 from .... import hipops as ops
 from ....hipops import pose_type_code, dims_func_code, pooler_type_code
 from ...util import math_util as util
-from ..backbone.fpn import c2_xavier_fill
+from ..backbone.fpn import c2_xavier_fill, to_channels_last
 from .cube_head import build_cube_head, fc_nhwc
 from .fast_rcnn import FastRCNNOutputs
 
@@ -68,15 +68,41 @@ class ROIPooler(nn.Module):
         return self.pool(x, rois)
 
 
+BOX_HEAD_NORMS = ("", "GN")
+
+
 @ROI_BOX_HEAD_REGISTRY.register()
 class FastRCNNConvFCHead(nn.Sequential):
-    """detectron2 FastRCNNConvFCHead with NUM_CONV 0 [third-party]: fc1 -> relu -> fc2 -> relu."""
+    """detectron2 FastRCNNConvFCHead [third-party, restated]: NUM_CONV x (conv 3x3 pad 1 -> norm -> relu), flatten,
+    NUM_FC x (fc -> relu).  conv_norm "" (convolutions with bias, ReLU in the conv epilogue) or "GN" (bias-free convolutions,
+    each with its own torch.nn.GroupNorm(32, CONV_DIM) registered as `conv{k}.norm`).  The convolutions run on the cr_conv2d_*
+    kernels over the RoI tiles as a batch (N = RoIs, H = W = pooler resolution)."""
 
     def __init__(self, input_shape: ShapeSpec, *, conv_dims, fc_dims, conv_norm=""):
         super().__init__()
-        assert len(conv_dims) == 0 and len(fc_dims) > 0
-        self._in_chw = (input_shape.channels, input_shape.height, input_shape.width)
-        self._output_size = self._in_chw
+        if conv_norm not in BOX_HEAD_NORMS:
+            raise ValueError('built: MODEL.ROI_BOX_HEAD.NORM "" / "GN"; got NORM "{}"'.format(conv_norm))
+        if len(fc_dims) == 0:
+            raise ValueError("built: MODEL.ROI_BOX_HEAD.NUM_FC >= 1 (the predictors read a flat feature); got NUM_FC 0")
+        self._output_size = (input_shape.channels, input_shape.height, input_shape.width)
+        self.conv_norm_relus = []
+        for k, conv_dim in enumerate(conv_dims):
+            cin = self._output_size[0]
+            pow2 = lambda v: v >= 8 and v & (v - 1) == 0
+            if not (pow2(cin) and pow2(conv_dim) and conv_dim % 16 == 0 and (conv_norm == "" or conv_dim % 32 == 0)):
+                raise ValueError("built: MODEL.ROI_BOX_HEAD.CONV_DIM (and the pooled channel count) a power of two >= 16 -- the "
+                                 "3x3 convolution kernels take a power-of-two input width in both directions and Cout % 16 == 0"
+                                 "{}; got conv{} {} -> {}".format(", GroupNorm(32) C % 32 == 0" if conv_norm else "", k + 1, cin,
+                                                                  conv_dim))
+            conv = nn.Conv2d(cin, conv_dim, kernel_size=3, padding=1, bias=conv_norm == "")
+            if conv_norm == "GN":
+                conv.norm = nn.GroupNorm(32, conv_dim)
+            self.add_module("conv{}".format(k + 1), conv)
+            self.conv_norm_relus.append(conv)
+            self._output_size = (conv_dim, self._output_size[1], self._output_size[2])
+        # fc1's weight columns keep the reference's (c,h,w) order over the NHWC-flattened map it is applied to
+        self._in_chw = self._output_size
+        self._conv_norm = conv_norm
         self.fcs = []
         for k, fc_dim in enumerate(fc_dims):
             fc = nn.Linear(int(np.prod(self._output_size)), fc_dim)
@@ -84,11 +110,22 @@ class FastRCNNConvFCHead(nn.Sequential):
             self.add_module("fc_relu{}".format(k + 1), nn.ReLU())
             self.fcs.append(fc)
             self._output_size = fc_dim
+        for layer in self.conv_norm_relus:             # fvcore c2_msra_fill
+            nn.init.kaiming_normal_(layer.weight, mode="fan_out", nonlinearity="relu")
+            if layer.bias is not None:
+                nn.init.constant_(layer.bias, 0)
         for layer in self.fcs:
             c2_xavier_fill(layer)
+        to_channels_last(self)
 
     def forward(self, x):
         """x (R, H, W, C) bf16."""
+        for conv in self.conv_norm_relus:
+            if self._conv_norm == "GN":
+                n = conv.norm
+                x = ops.conv_gn_act(x, conv.weight, (n.weight, n.bias, n.num_groups, n.eps), 1, 1, relu=True)
+            else:
+                x = ops.conv_bias_act(x, conv.weight, conv.bias, 1, 1, relu=True)
         h = fc_nhwc(x.flatten(1), self.fcs[0], self._in_chw, relu=True)
         for fc in self.fcs[1:]:
             h = ops.linear(h, fc.weight, fc.bias, relu=True)

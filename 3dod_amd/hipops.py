@@ -1037,6 +1037,127 @@ def conv_bias_act(x, weight, bias, stride=1, pad=0, relu=False, out_f32=False):
 
 
 # --------------------------------------------------------------------------
+# GroupNorm over NHWC maps (csrc/groupnorm.hip): the norm "GN" of the FPN and of the conv box head.  No running statistics:
+# eval mode is the same call.  Workspaces come from torch's allocator and nothing waits on the host, so the calls can be
+# captured into the dense region's graph.
+# --------------------------------------------------------------------------
+def _gn_dims(x):
+    N, C = x.shape[0], x.shape[-1]
+    return N, x.numel() // max(1, N * C), C
+
+
+def _gn_workspace(x):
+    N, HW, C = _gn_dims(x)
+    n = _lib.groupnorm_ws_floats(N, HW, C)      # 0 outside the domain: the library then refuses the call itself
+    return torch.empty((max(n, 4),), dtype=f32, device=x.device), n
+
+
+def group_norm_fwd_raw(x, gamma, beta, groups, eps, relu=False, stat_rows=None):
+    """x (N, ..., C) NHWC -> y, mean_rstd (N, G, 2).  stat_rows: the [N * HW / 64][2][C] rows conv_fwd_raw(stats=) wrote for x
+    (HW % 64 == 0), instead of a statistics pass over x"""
+    _need_cuda(x, "group_norm input")
+    assert x.is_contiguous() and gamma.dtype == f32 and beta.dtype == f32
+    N, HW, C = _gn_dims(x)
+    y = torch.empty_like(x)
+    mr = torch.empty((N, max(1, groups), 2), dtype=f32, device=x.device)
+    ws, n = _gn_workspace(x)
+    _lib.call("cr_groupnorm_fwd", x, gamma, beta, stat_rows, y, mr, ws, n, N, HW, C, groups, float(eps), int(relu), _af(x))
+    return y, mr
+
+
+def group_norm_bwd_raw(dy, x, y, mean_rstd, gamma, groups, relu, dgamma, dbeta):
+    """-> dx; dgamma / dbeta (C) f32 are accumulated into.  y: the stored output (read only with relu)"""
+    assert dy.is_contiguous() and x.is_contiguous() and dy.dtype == x.dtype
+    N, HW, C = _gn_dims(x)
+    dx = torch.empty_like(x)
+    ws, n = _gn_workspace(x)
+    _lib.call("cr_groupnorm_bwd", dy, x, y if relu else None, mean_rstd, gamma, ws, n, dx, dgamma, dbeta, N, HW, C, groups,
+              int(relu), _af(x))
+    return dx
+
+
+def _gn_param_acc(ctx_needs, gamma, beta, C, dev):
+    """(accumulators, autograd returns) of dgamma / dbeta: the parameters' gradient sinks where both have one"""
+    gs, bs = grad_sink(gamma), grad_sink(beta)
+    if gs is not None and bs is not None:
+        return (gs, bs), (None, None)
+    fresh = tuple(torch.zeros((C,), dtype=f32, device=dev) for _ in range(2))
+    return fresh, tuple(f if need else None for f, need in zip(fresh, ctx_needs))
+
+
+class _GroupNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, groups, eps, relu):
+        x = x.contiguous()
+        y, mr = group_norm_fwd_raw(x, gamma.detach(), beta.detach(), groups, eps, relu)
+        ctx.cfg = (groups, relu)
+        ctx.beta_ref = beta
+        ctx.save_for_backward(x, gamma, mr, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, mr, y = ctx.saved_tensors
+        groups, relu = ctx.cfg
+        acc, ret = _gn_param_acc(ctx.needs_input_grad[1:3], gamma, ctx.beta_ref, x.shape[-1], x.device)
+        dx = group_norm_bwd_raw(_act_cast(dy, x.dtype), x, y, mr, gamma.detach(), groups, relu, *acc)
+        return dx, ret[0], ret[1], None, None, None
+
+
+def group_norm(x, gamma, beta, groups, eps=1e-5, relu=False):
+    """relu?(GroupNorm(groups, C)(x)) of an NHWC map in the activation dtype; gamma / beta (C) f32 parameters.  dgamma / dbeta
+    go into the parameters' gradient sinks where they exist (autograd then sees None), else they are returned."""
+    return _GroupNorm.apply(x, gamma, beta, groups, eps, relu)
+
+
+class _ConvGN(torch.autograd.Function):
+    """bias-free convolution, then GroupNorm (+ ReLU).  In float32, when a sample's output map is a multiple of 128 pixels, the
+    convolution's epilogue writes the statistics rows and GroupNorm never reads the map for them.  128, not 64: the
+    convolution's 128-pixel tiles put their sums into every second row, and no tile may straddle two samples.  Not in bf16:
+    the epilogue sums the float32 accumulators, GroupNorm normalises the bf16-rounded map it is handed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, groups, eps, stride, pad, relu, slot=(None, 0)):
+        ctx.slot = slot
+        Cout, Cin, k, _ = weight.shape
+        wb, _ = prepared_weights(weight, False, x.dtype)
+        N, H, W, _ = x.shape
+        HWo = ((H + 2 * pad - k) // stride + 1) * ((W + 2 * pad - k) // stride + 1)
+        rows = torch.empty((N * HWo // 64, 2, Cout), dtype=f32, device=x.device) if HWo % 128 == 0 and x.dtype == f32 else None
+        t = conv_fwd_raw(x, wb, Cout, k, stride, pad, stats=rows)
+        y, mr = group_norm_fwd_raw(t, gamma.detach(), beta.detach(), groups, eps, relu, stat_rows=rows)
+        ctx.cfg = (k, stride, pad, relu, groups)
+        ctx.beta_ref = beta
+        ctx.save_for_backward(x, weight, gamma, t, mr, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, gamma, t, mr, y = ctx.saved_tensors
+        k, stride, pad, relu, groups = ctx.cfg
+        acc, ret = _gn_param_acc(ctx.needs_input_grad[2:4], gamma, ctx.beta_ref, t.shape[-1], x.device)
+        g = group_norm_bwd_raw(_act_cast(dy, t.dtype), t, y, mr, gamma.detach(), groups, relu, *acc)
+        dx = None
+        xslot, xi = ctx.slot
+        if ctx.needs_input_grad[0]:
+            _, wt = prepared_weights(weight, True, x.dtype)
+            if xslot is not None and xi > 1:
+                _slot_put(xslot, conv_bwd_data_raw(g, wt, x.shape, k, stride, pad, accumulate=_slot_fold(xslot)))
+            else:
+                dx = conv_bwd_data_raw(g, wt, x.shape, k, stride, pad, accumulate=_slot_take(xslot) if xslot is not None else None)
+        elif xslot is not None:
+            raise RuntimeError("gradient slot registered for an input that needs no gradient")
+        dw = conv_bwd_weight_raw(g, x, k, stride, pad, grad_sink(weight)) if ctx.needs_input_grad[1] else None
+        return dx, dw, ret[0], ret[1], None, None, None, None, None, None
+
+
+def conv_gn_act(x, weight, gn_args, stride=1, pad=0, relu=False):
+    """relu?(GroupNorm(conv(x, weight))): a bias-free convolution followed by GroupNorm; gn_args = (gamma, beta, groups, eps)"""
+    gamma, beta, groups, eps = gn_args
+    return _ConvGN.apply(x, as_krsc(weight), gamma, beta, groups, eps, stride, pad, relu, _slot_register(x, True))
+
+
+# --------------------------------------------------------------------------
 # grouped convolutions: the five pyramid levels of an FPN output conv / the RPN head conv in ONE launch per direction
 # --------------------------------------------------------------------------
 _GROUP_ON = [os.environ.get("CR_CONV_GROUP", "1") == "1"]

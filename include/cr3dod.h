@@ -607,6 +607,35 @@ int cr_bn_pair_bwd(cr_ctx* ctx, const void* dout, const void* out, const void* y
                    void* dxa_raw, void* dxb_raw, float* dgamma_a, float* dbeta_a, float* dgamma_b, float* dbeta_b, int64_t M,
                    int C, int act_f32);
 
+/* GroupNorm over NHWC maps (csrc/groupnorm.hip): torch.nn.GroupNorm(G, C), optionally followed by ReLU -- detectron2's norm
+ * "GN" of the FPN (MODEL.FPN.NORM) and of the conv box head (MODEL.ROI_BOX_HEAD.NORM) [third-party, restated].  There are no
+ * running statistics: eval mode is the same arithmetic.
+ *   x, y, dy, dx (N, HW, C) bf16 or f32 (act_f32 != 0; 1 and 2 are the same here), 16-byte aligned; gamma, beta (C) f32;
+ *   mean_rstd (N, G, 2) f32 = mean | 1 / sqrt(biased var + eps) per (sample, group).
+ * Domain: C % 32 == 0, 32 <= C <= 2048, C % G == 0 (any C / G >= 1), N, HW >= 1, relu in {0, 1}; anything else, a NULL or
+ * misaligned pointer or a short workspace returns CR_EINVAL without a launch.
+ * Per-channel pixel sums are float32 per 64 pixels; rows, the channels of a group and samples are added in double in a fixed
+ * order.  No atomics: bit-identical from run to run.  HW <= 64 and C <= 512 (RoI tiles) run as one launch in which a workgroup
+ * owns whole samples (forward; the backward adds one launch for dgamma / dbeta); everything else as statistics rows -> finalize
+ * -> apply.
+ *   fwd  y = relu?((x - mean) * (gamma * rstd) + beta); a group of equal values gives exactly beta.
+ *        stat_rows: NULL, or f32 [N * HW / 64][2][C], the per-64-pixel sums / sums of squares a convolution's epilogue wrote
+ *        for x (cr_conv2d_fwd stats); needs HW % 64 == 0 (no row straddles two samples); x is then read once.  Only the sum
+ *        of a sample's HW / 64 rows matters (a 128-pixel convolution tile fills every second row), so the caller must also
+ *        know that no tile of the convolution straddled two samples (HW % 128 == 0) and that x holds the summed values
+ *        (float32 output; a bf16 map is rounded after the epilogue summed it).
+ *   bwd  g = dy * [y > 0] with relu (y = the stored output, required then; ignored without relu);
+ *        dx = gamma rstd g + B (x - mean) + D per (sample, group); dgamma / dbeta (C) are accumulated (+=).
+ *   ws   f32, 16-byte aligned, at least cr_groupnorm_ws_floats(N, HW, C) = N * C * (2 * ceil(HW / 64) + 6) floats (a host-side
+ *        count, no context and no status; 0 outside the domain or beyond INT_MAX).  Written and read by the call's own launches. */
+int cr_groupnorm_ws_floats(int64_t N, int64_t HW, int C);
+int cr_groupnorm_fwd(cr_ctx* ctx, const void* x, const float* gamma, const float* beta, const float* stat_rows, void* y,
+                     float* mean_rstd, float* ws, int64_t ws_floats, int N, int64_t HW, int C, int G, float eps, int relu,
+                     int act_f32);
+int cr_groupnorm_bwd(cr_ctx* ctx, const void* dy, const void* x, const void* y, const float* mean_rstd, const float* gamma,
+                     float* ws, int64_t ws_floats, void* dx, float* dgamma, float* dbeta, int N, int64_t HW, int C, int G,
+                     int relu, int act_f32);
+
 /* FC weights of the RoI heads (roi_heads.py:2160-2204, cube_head.py:152-202).  w f32 (O, C, HW) in the checkpoint's
  * (c,h,w) column order -> wb bf16 (O, HW, C) for NHWC-flattened inputs (HW = 1: plain cast); and the transpose for the
  * gradient: acc f32 (O, C, HW) += g bf16 (O, HW, C). */

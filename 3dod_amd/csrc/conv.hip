@@ -3406,6 +3406,9 @@ extern "C" int cr_weights_prepare(cr_ctx* ctx, const float* src_base, void* dst_
 // A block handles one output row and a tile of 64 input channels: both sides move whole contiguous runs.
 // ---------------------------------------------------------------------------
 #define FC_CT 64
+// The tile is dynamic LDS of FC_CT * (HW + 1) floats and no attribute raises the 64 KB a launch gets by default, so the entry
+// points take HW <= 255 (65 536 B exactly); the poolers in use are 7x7 (49) and 14x14 (196).
+#define FC_HW_MAX 255
 template <typename T>
 __global__ __launch_bounds__(256) void k_fc_weight_prepare(const float* __restrict__ src, T* __restrict__ dst, int C, int HW) {
     extern __shared__ float s_fc[];                       // [FC_CT][HW + 1]
@@ -3463,7 +3466,8 @@ __global__ void k_axpy_bf16_f32(const u16* __restrict__ g, float* __restrict__ a
 }
 
 extern "C" int cr_fc_weight_prepare(cr_ctx* ctx, const float* w, void* wb, int O, int C, int HW, int act_f32) {
-    CR_CHECK_ARG(ctx && w && wb && O > 0 && C > 0 && HW > 0 && HW <= 1024, "cr_fc_weight_prepare: bad args");
+    CR_CHECK_ARG(ctx && w && wb && O > 0 && C > 0 && HW > 0 && HW <= FC_HW_MAX,
+                 "cr_fc_weight_prepare: bad args (HW in 1..%d)", FC_HW_MAX);
     if (HW == 1) {
         if (!act_f32) return cr_cast_f32_to_bf16(ctx, w, wb, (int64_t)O * C);
         CR_HIP(hipMemcpyAsync(wb, w, (size_t)O * C * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
@@ -3480,7 +3484,8 @@ extern "C" int cr_fc_weight_prepare(cr_ctx* ctx, const float* w, void* wb, int O
 }
 
 extern "C" int cr_fc_grad_accum(cr_ctx* ctx, const void* g, float* acc, int O, int C, int HW, int act_f32) {
-    CR_CHECK_ARG(ctx && g && acc && O > 0 && C > 0 && HW > 0 && HW <= 1024, "cr_fc_grad_accum: bad args");
+    CR_CHECK_ARG(ctx && g && acc && O > 0 && C > 0 && HW > 0 && HW <= FC_HW_MAX,
+                 "cr_fc_grad_accum: bad args (HW in 1..%d)", FC_HW_MAX);
     if (HW == 1) {
         const int64_t n = (int64_t)O * C;
         CR_CHECK_ARG((((uintptr_t)g) & 7) == 0 && (((uintptr_t)acc) & 15) == 0, "cr_fc_grad_accum: misaligned");

@@ -638,7 +638,8 @@ int cr_groupnorm_bwd(cr_ctx* ctx, const void* dy, const void* x, const void* y, 
 
 /* FC weights of the RoI heads (roi_heads.py:2160-2204, cube_head.py:152-202).  w f32 (O, C, HW) in the checkpoint's
  * (c,h,w) column order -> wb bf16 (O, HW, C) for NHWC-flattened inputs (HW = 1: plain cast); and the transpose for the
- * gradient: acc f32 (O, C, HW) += g bf16 (O, HW, C). */
+ * gradient: acc f32 (O, C, HW) += g bf16 (O, HW, C).  act_f32: wb / g are f32 instead.  1 <= HW <= 255: a block stages
+ * 64 channels x (HW + 1) floats in the 64 KB of dynamic LDS a launch gets by default (the poolers in use: 7x7, 14x14). */
 int cr_fc_weight_prepare(cr_ctx* ctx, const float* w, void* wb, int O, int C, int HW, int act_f32);
 int cr_fc_grad_accum(cr_ctx* ctx, const void* g, float* acc, int O, int C, int HW, int act_f32);
 

@@ -8,9 +8,11 @@ add up like a random walk).  The size of the terms at an output element is absre
     |got - ref| <= C * u * sqrt(K) * absref + TINY
 
 with ref and absref computed in float64 by ATen.  K is taps * Cin for the forward pass, taps * Cout for the backward-data
-pass and N * Ho * Wo for the weight (and bias) gradient.  The bound is local: an error confined to one tile, one channel
-or one split of a reduce shows at the element where it happens instead of averaging into a norm over the whole tensor,
-and so does an operand that lost a few bits (tests/test_f64_bound.py shows all three failing it).
+pass and N * Ho * Wo for the weight (and bias) gradient; for a linear layer over R rows that is K, O and R.  The bound is
+local: an error confined to one tile, one channel or one split of a reduce shows at the element where it happens instead
+of averaging into a norm over the whole tensor, and so does an operand that lost a few bits (tests/test_f64_bound.py shows
+all three failing it).  `linear_*` are the same three directions of a linear layer, and `check_bf16_out` is the bound for
+bfloat16 operands with a bfloat16-stored result.
 
 Winograd F(2x2, 3x3) adds transforms around its contraction, and the products it sums are of transformed operands whose
 magnitudes exceed those of the direct form; `wino_fwd` / `wino_wgrad` with absval=True give the matching absref (see
@@ -78,6 +80,73 @@ def conv_bwd_weight(dy, x, w_shape, stride, pad):
 def bias_grad(dy):
     dy = dy.to(f64)
     return dy.sum((0, 2, 3)), dy.abs().sum((0, 2, 3)), dy.shape[0] * dy.shape[2] * dy.shape[3]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# linear layers (the GEMM family behind cr_linear_*): (ref, absref, K) of the three directions, float64, computed on the
+# device of the inputs (the large cases take torch's own float64 matmul on the GPU, which shares nothing with the kernels
+# under test).  x (R, K), w (O, K), dy (R, O).
+# ---------------------------------------------------------------------------------------------------------------------
+def linear_fwd(x, w, b):
+    x, w = x.to(f64), w.to(f64)
+    ref, absref = x @ w.t(), x.abs() @ w.abs().t()
+    if b is not None:
+        ref, absref = ref + b.to(f64), absref + b.to(f64).abs()
+    return ref, absref, x.shape[1]
+
+
+def linear_bwd_data(dy, w):
+    dy, w = dy.to(f64), w.to(f64)
+    return dy @ w, dy.abs() @ w.abs(), w.shape[0]
+
+
+def linear_bwd_weight(dy, x):
+    dy, x = dy.to(f64), x.to(f64)
+    return dy.t() @ x, dy.abs().t() @ x.abs(), dy.shape[0]
+
+
+def linear_bias_grad(dy):
+    dy = dy.to(f64)
+    return dy.sum(0), dy.abs().sum(0), dy.shape[0]
+
+
+U_BF16 = 2.0 ** -8      # bfloat16 unit roundoff (8 significand bits, round to nearest even)
+
+
+def report_bf16_out(got, ref, absref, K, c=C):
+    """report() for a result that was accumulated in float32 and then stored as bfloat16; "ratio" is scaled so that the
+    bound of check_bf16_out is ratio <= c, like report()'s"""
+    got = got.detach().to(ref.device, f64)
+    assert got.shape == ref.shape == absref.shape, (tuple(got.shape), tuple(ref.shape), tuple(absref.shape))
+    err = (got - ref).abs()
+    b1 = U * math.sqrt(K) * absref                                  # the float32 bound at c = 1
+    scale = b1 + U_BF16 * (ref.abs() / c + b1)                      # c * scale = B + 2^-8 (|ref| + B) with B = c * b1
+    bad = (err > c * scale + TINY * (1 + U_BF16)) | torch.isnan(got)
+    ratio = err / (scale + TINY)
+    ratio = torch.where(torch.isnan(got), torch.full_like(ratio, float("inf")), ratio)
+    i = int(ratio.flatten().argmax())
+    idx = tuple(int(v) for v in torch.unravel_index(torch.tensor(i), ref.shape))
+    return {"ratio": float(ratio.flatten()[i]), "bad": int(bad.sum()), "n": ref.numel(), "where": idx,
+            "got": float(got.flatten()[i]), "ref": float(ref.flatten()[i]), "absref": float(absref.flatten()[i]),
+            "norm": float((got - ref).norm() / (ref.norm() + 1e-300)), "K": K}
+
+
+def check_bf16_out(got, ref, absref, K, what, c=C):
+    """the bound for bfloat16 operands and a bfloat16-stored result.  ref / absref are computed from the operands AFTER
+    their rounding to bfloat16.  A product of two bfloat16 values has 16 significand bits and is exact in float32, so the
+    float32 accumulator v obeys the float32 bound unchanged: |v - ref| <= B, B = c * U * sqrt(K) * absref + TINY (which
+    is what check() asks of an output kept in float32: out_f32, dw, dbias).  Storing v as bfloat16 rounds once more, to
+    nearest: |got - v| <= 2^-8 |v| <= 2^-8 (|ref| + B).  Together
+
+        |got - ref| <= B + 2^-8 * (|ref| + B)
+
+    A ReLU between the accumulator and the store commutes with the rounding and does not increase |v - ref| when ref is
+    passed through the same ReLU."""
+    r = report_bf16_out(got, ref, absref, K, c)
+    assert r["bad"] == 0, f"{what}: {r['bad']} of {r['n']} elements over the bf16-output bound; worst ratio {r['ratio']:.3g} > {c} " \
+                          f"at index {r['where']} (got {r['got']:.9g}, ref {r['ref']:.9g}, absref {r['absref']:.4g}, K {K}); " \
+                          f"normwise {r['norm']:.3g}"
+    return r
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -307,7 +307,7 @@ def test_gradient_slots_equal_autograd_adds():
 def test_linear_head_fc1_full_size():
     """the box head's first FC layer at the train step's size (2048 RoIs x 12544 -> 1024): the forward takes the long-k
     split (128 x 128 tiles, 4 k ranges + epilogue), the weight gradient 64-row tiles with two row splits (1568 tiles);
-    against torch's f32 GEMM (same arithmetic up to summation order)."""
+    against torch's f32 GEMM (same arithmetic up to summation order), then every element against float64."""
     g = torch.Generator(device=DEV).manual_seed(3)
     R, K, O = 2048, 12544, 1024
     x = torch.randn(R, K, device=DEV, generator=g)
@@ -323,3 +323,12 @@ def test_linear_head_fc1_full_size():
     ops.linear_bwd_weight_raw(dy, x, dw, db, True)
     assert relerr(dw, dy.t() @ x) < 2e-5
     assert relerr(db, dy.sum(0)) < 2e-5
+    # ... and every element against float64 (torch's float64 GEMM on the device), bound of tests/f64_bound.py
+    import f64_bound as B
+    pre, absref, k = B.linear_fwd(x, w, b)
+    r = [B.check(y, torch.relu(pre), absref, k, "FC1 forward, long-k split")]
+    del pre, absref
+    r.append(B.check(dx, *B.linear_bwd_data(dy, w), "FC1 backward-data"))
+    r.append(B.check(dw, *B.linear_bwd_weight(dy, x), "FC1 weight gradient"))
+    r.append(B.check(db, *B.linear_bias_grad(dy), "FC1 bias gradient"))
+    print("RATIO FC1 full size y / dx / dw / db: " + " / ".join(f"{q['ratio']:.3f}" for q in r))

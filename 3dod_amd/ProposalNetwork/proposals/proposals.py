@@ -82,6 +82,46 @@ def propose_batched(boxes, img_idx, depth_images, priors, K, number_of_proposals
     raise RuntimeError("truncated-normal rejection sampling did not converge (prior std too large for its range?)")
 
 
+def propose_variant_batched(name, boxes, img_idx, depth_images, priors, K, im_shape, number_of_proposals, generator=None,
+                            defer_check=False):
+    """The ablation sampler `name` ('random', 'xy', 'z', 'dim', 'aspect', 'rotation', reference proposals.py:20-336) for the
+    objects of a whole batch in one launch (cr_propose_sampler_batched), the counterpart of propose_batched: boxes (N,4)
+    tensor, img_idx (N) int32, depth_images (B,H,W), priors = (mean (N,3), std (N,3)), K (B,3,3), im_shape (width, height).
+    Every variate is drawn on the boxes' device from `generator` (torch.randint(7) for the aspect-ratio indices:
+    randperm(7)[0] of the reference is uniform over 7); no loop over images or objects and no read-back except the
+    'rotation' sampler's exhausted flag, which follows propose_batched's rule (`_rounds_hint`, `note_exhausted`,
+    defer_check).  'z': an object with an empty depth patch gets NaN z where the reference raises.  Returns the (N,P,15)
+    cube tensor, or (cubes, exhausted) with defer_check=True."""
+    if name not in geo.SAMPLER_MODES:
+        raise ValueError(f"unknown batched proposal function '{name}' (one of {sorted(geo.SAMPLER_MODES)})")
+    dev = boxes.device
+    N, P = boxes.shape[0], int(number_of_proposals)
+    if N == 0:
+        z = torch.zeros((0, P, 15), device=dev)
+        return (z, torch.zeros((1,), dtype=torch.int32, device=dev)) if defer_check else z
+    mu, sg = priors[0].to(dev).float(), priors[1].to(dev).float()
+    depth = depth_images.to(dev).float().contiguous()
+    U = geo.SAMPLER_UNIFORMS[name]
+    draws = dict(basis=torch.randn((N, P, 3, 3), device=dev, generator=generator))
+    if U:
+        draws["uniforms"] = torch.rand((U, N, P), device=dev, generator=generator)
+    if name in ("dim", "aspect", "rotation"):
+        draws["ctr_normals"] = torch.randn((3, N, P), device=dev, generator=generator)
+    if name == "aspect":
+        draws["ratio_idx"] = torch.randint(7, (N, 2), device=dev, generator=generator, dtype=torch.int32)
+    for attempt in range(12):
+        if name == "rotation":
+            draws["dim_normals"] = torch.randn((_rounds_hint[0], 3, N, P), device=dev, generator=generator)
+        cubes, exhausted = geo.propose_sampler_from_draws_batched(name, boxes.float().contiguous(), img_idx, depth, mu, sg,
+                                                                  K.to(dev).float().contiguous(), im_shape, P, **draws)
+        if defer_check:
+            return cubes, exhausted
+        if name != "rotation" or int(exhausted.item()) == 0:
+            return cubes
+        note_exhausted()
+    raise RuntimeError("truncated-normal rejection sampling did not converge (prior std too large for its range?)")
+
+
 def note_exhausted():
     """the last propose ran out of rejection rounds: wide priors reject often, so start the next one with twice as many"""
     if _rounds_hint[0] >= 8192:
@@ -91,9 +131,12 @@ def note_exhausted():
 
 # ---------------------------------------------------------------------------------------------------------------
 # The ablation samplers of the reference (proposals.py:20-336) and the coverage statistics (:427-447).  They are
-# selected by name through ROIHeads_Boxer.predict_cubes(proposal_function=...) (roi_heads.py:283-302) and are not on the
-# hot path: plain tensor expressions on the boxes' device, written in the reference's order of operations AND of random
-# draws (utils.Draws), so that the recorded-draws goldens replay them (tests/golden/proposals_variants.npz).
+# selected by name through ROIHeads_Boxer.predict_cubes(proposal_function=...) (roi_heads.py:283-302): the single-image
+# route of the MABO / gt_cubes statistics, and the CPU restatement of the samplers -- plain tensor expressions on the
+# boxes' device, written in the reference's order of operations AND of random draws (utils.Draws), so that the
+# recorded-draws goldens replay them (tests/golden/proposals_variants.npz).  The AP path of ROIHeads_Boxer._forward_cube
+# does not come through here: it runs the same samplers for the whole batch on cr_propose_sampler_batched
+# (propose_variant_batched above), whose operation order these functions define.
 # ---------------------------------------------------------------------------------------------------------------
 from ..utils import utils as _U                      # noqa: E402
 from ..utils.conversions import pixel_to_normalised_space    # noqa: E402

@@ -27,6 +27,8 @@ SIGNATURES = {
     "cr_ransac_plane": [P, P, c_int64, P, c_int64, c_float, P, P, P],
     "cr_ransac_plane_batched": [P, P, P, c_int, c_int64, P, c_int64, c_float, P, P, P],
     "cr_propose_batched": [P, P, P, c_int64, P, c_int, c_int, c_int, P, P, P, c_int64, P, c_int, P, P, P, P, P],
+    "cr_propose_sampler_batched": [P, c_int, P, P, c_int64, P, c_int, c_int, c_int, P, P, P, c_float, c_float, c_int64, P, P, P,
+                                   c_int, P, P, P, P],
     "cr_box_median": [P, P, c_int, c_int, c_int, P, P, c_int, P],
     "cr_fold_bn": [P, P, P, P, P, P, c_float, P, P, c_int, c_int, c_int],
     "cr_hull8": [P, P, c_int, P, P, P],

@@ -22,7 +22,9 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno
 # contract with oracle/geometry.py -> no fused multiply-add contraction.
 # dense_train.hip: two kernels must reproduce the same IoU bits (equality test of allow_low_quality_matches).
 # weak.hip: the hull march compares float32 cross products for exact ties like the reference's tensor arithmetic.
-EXTRA = {"geometry.hip": ["-ffp-contract=off"], "dense_train.hip": ["-ffp-contract=off"], "weak.hip": ["-ffp-contract=off"]}
+# propose_samplers.hip: like geometry.hip, the float32 op order of the samplers is part of the parity with the reference.
+EXTRA = {"geometry.hip": ["-ffp-contract=off"], "dense_train.hip": ["-ffp-contract=off"], "weak.hip": ["-ffp-contract=off"],
+         "propose_samplers.hip": ["-ffp-contract=off"]}
 
 
 def _newer(a, b):

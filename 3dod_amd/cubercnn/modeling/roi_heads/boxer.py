@@ -177,7 +177,8 @@ class ROIHeads_Boxer(StandardROIHeads):
         prior = self.priors_dims_per_cat.detach()[0][torch.cat(list(classes))]   # (Ntot,2,3)
         mu, sg = prior[:, 0, :].contiguous(), prior[:, 1, :].contiguous()
 
-        normals = self._ground_normals(depth_maps, ground_maps, K_img, generator)  # (B,3)
+        # (B,3); the ablation samplers orient their cubes by a random basis and take no ground normal
+        normals = self._ground_normals(depth_maps, ground_maps, K_img, generator) if proposal_function == 'propose' else None
 
         rects = None
         if masks is not None and any(m is not None for m in masks):
@@ -202,16 +203,12 @@ class ROIHeads_Boxer(StandardROIHeads):
                 cubes_t, exhausted = PN.propose_batched(ref, img_idx, depth_maps, (mu, sg), K_img, P, normals,
                                                         generator=generator, defer_check=True)
             else:
-                # an ablation sampler (roi_heads.py:286-297): image by image, as the reference does
-                parts, o = [], 0
-                for i, n in enumerate(counts):
-                    if n:
-                        c, _, _, _ = self.predict_cubes(boxes[i], (mu[o:o + n], sg[o:o + n]), depth_maps[i], (W, H), K_img[i],
-                                                        proposal_function, normals[i], generator=generator)
-                        parts.append(c.tensor.to(dev))
-                    o += n
-                cubes_t = torch.cat(parts).contiguous()
-                exhausted = torch.zeros((1,), dtype=torch.int32, device=dev)
+                # an ablation sampler (roi_heads.py:286-297): one launch for the batch as well (cr_propose_sampler_batched)
+                if proposal_function not in PN.PROPOSAL_FUNCTIONS:
+                    raise ValueError(f"unknown proposal function '{proposal_function}' "
+                                     f"(one of {sorted(PN.PROPOSAL_FUNCTIONS)})")
+                cubes_t, exhausted = PN.propose_variant_batched(proposal_function, ref, img_idx, depth_maps, (mu, sg), K_img,
+                                                                (W, H), P, generator=generator, defer_check=True)
             res = geo.cubes_project_score(cubes_t, K_obj, (W, H), ref, mu, sg, rects, want=(), iou_boxes=iou_ref)
             idx = res["argmax"]
             best = cubes_t[torch.arange(cubes_t.shape[0], device=dev), idx]    # (Ntot,15)

@@ -131,6 +131,61 @@ def propose_from_draws_batched(boxes, img_idx, depth, prior_mu, prior_sigma, K, 
     return cubes, exhausted
 
 
+SAMPLER_MODES = {"random": 0, "xy": 1, "z": 2, "dim": 3, "aspect": 4, "rotation": 5}      # CR_SAMPLER_* of cr3dod.h
+SAMPLER_UNIFORMS = {"random": 6, "xy": 4, "z": 3, "dim": 3, "aspect": 1, "rotation": 0}
+
+
+def propose_sampler_from_draws_batched(mode, boxes, img_idx, depth, prior_mu, prior_sigma, K, im_shape, P, uniforms=None,
+                                       ctr_normals=None, dim_normals=None, ratio_idx=None, basis=None):
+    """cr_propose_sampler_batched: the ablation sampler `mode` ('random', 'xy', 'z', 'dim', 'aspect', 'rotation') for the
+    objects of B images in one launch, with caller-supplied variates.  boxes (N,4), img_idx (N) int32, depth (B,H,W),
+    prior_mu / prior_sigma (N,3), K (B,3,3), im_shape = (width, height).  Draws, each only for the modes that take it (see
+    cr3dod.h): uniforms (U,N,P) with U = 6 / 4 / 3 / 3 / 1 for random / xy / z / dim / aspect, ctr_normals (3,N,P) for dim /
+    aspect / rotation, dim_normals (rounds,3,N,P) for rotation, ratio_idx (N,2) int32 in [0,7) for aspect, basis (N,P,3,3)
+    standard normals always.  Returns (cubes (N,P,15), exhausted int tensor).
+
+    mode 'z': an object whose depth patch holds a NaN gets NaN z, as torch.quantile gives; an object whose patch
+    depth[int(y1):int(y2), int(x1):int(x2)] is EMPTY, where the reference raises, gets NaN z too and the call succeeds."""
+    if mode not in SAMPLER_MODES:
+        raise ValueError(f"unknown sampler '{mode}' (one of {sorted(SAMPLER_MODES)})")
+    boxes = _f32c(boxes, "boxes", (None, 4))
+    N, dev, P = boxes.shape[0], boxes.device, int(P)
+    depth = _f32c(depth, "depth", (None, None, None))
+    B, H, W = depth.shape
+    K = _f32c(K, "K", (B, 3, 3))
+    prior_mu = _f32c(prior_mu, "prior_mu", (N, 3))
+    prior_sigma = _f32c(prior_sigma, "prior_sigma", (N, 3))
+    img_idx = img_idx.to(device=dev, dtype=torch.int32).contiguous()
+    assert tuple(img_idx.shape) == (N,)
+    U, rays = SAMPLER_UNIFORMS[mode], mode in ("dim", "aspect", "rotation")
+
+    def draw(t, name, shape, need):
+        if not need:
+            return None
+        if t is None:
+            raise ValueError(f"sampler '{mode}' takes {name} {shape}")
+        return _f32c(t, name, shape)
+
+    uniforms = draw(uniforms, "uniforms", (U, N, P), U > 0)
+    ctr_normals = draw(ctr_normals, "ctr_normals", (3, N, P), rays)
+    dim_normals = draw(dim_normals, "dim_normals", (None, 3, N, P), mode == "rotation")
+    basis = draw(basis, "basis", (N, P, 3, 3), True)
+    rounds = dim_normals.shape[0] if dim_normals is not None else 0
+    if mode == "aspect":
+        if ratio_idx is None:
+            raise ValueError("sampler 'aspect' takes ratio_idx (N,2)")
+        ratio_idx = ratio_idx.to(device=dev, dtype=torch.int32).contiguous()
+        assert tuple(ratio_idx.shape) == (N, 2)
+    else:
+        ratio_idx = None
+    cubes = torch.empty((N, P, 15), dtype=f32, device=dev)
+    exhausted = torch.zeros((1,), dtype=torch.int32, device=dev)
+    _lib.call("cr_propose_sampler_batched", SAMPLER_MODES[mode], boxes, img_idx, N, depth, B, H, W, prior_mu, prior_sigma, K,
+              float(im_shape[0]), float(im_shape[1]), P, uniforms, ctr_normals, dim_normals, rounds, ratio_idx, basis, cubes,
+              exhausted)
+    return cubes, exhausted
+
+
 def ransac_plane_batched(pts, triples, eligible=None, thresh=0.05):
     """B plane fits at once (cr_ransac_plane_batched): pts (B,Q,3), triples (B,T,3) int32 indices of eligible points,
     eligible (B,Q) bool/uint8 or None.  Returns (-equation (B,4), counts (B,T), best (B,2) = idx,count).  The caller

@@ -122,6 +122,39 @@ int cr_propose_batched(cr_ctx* ctx, const float* boxes, const int32_t* img_idx, 
                        int64_t P, const float* dim_normals, int rounds, const float* ctr_normals,
                        const int32_t* yaw_idx, const float* normals, float* out_cubes, int32_t* out_exhausted);
 
+/* The six ablation samplers of ProposalNetwork/proposals/proposals.py:20-336 (chosen by name in
+ * cubercnn/modeling/roi_heads/roi_heads.py:283-302) for the objects of B images in one launch, one workgroup per object,
+ * with every random variate supplied by the caller like cr_propose.  mode:
+ *   CR_SAMPLER_RANDOM   (:20-45)    x = 4u-2, y = 2u-1, z = 4u+1, w/h/l = (0.05-2)u+2; uniforms (6,N,P) in that order
+ *   CR_SAMPLER_XY       (:47-91)    x / y on lines through the inner half of the box in normalised image space
+ *                                   (conversions.py:50-67 on im_w / im_h, utils.py:170-177); uniforms (4,N,P) = z, w, h, l
+ *   CR_SAMPLER_Z        (:93-135)   as XY, z = torch.linspace(q10, q90, P) of the depth patch
+ *                                   depth[int(y1):int(y2), int(x1):int(x2)] (Python slice rules, torch.quantile's linear
+ *                                   interpolation in float32, exact selection); uniforms (3,N,P) = w, h, l
+ *   CR_SAMPLER_DIM      (:137-197)  centre from the depth rays as cr_propose (lower median, unbiased std, ctr_normals
+ *                                   (3,N,P)); uniforms (3,N,P) = w, h, l
+ *   CR_SAMPLER_ASPECT   (:199-270)  as DIM with w uniform, h = w r[i1], l = w r[i2], r = (0.33, 0.66, 1, 1.33, 1.67, 2, 3);
+ *                                   uniforms (1,N,P), ratio_idx (N,2) int32 in [0,7)
+ *   CR_SAMPLER_ROTATION (:272-336, = `propose` without a ground normal :398-400)  centre and truncated-normal
+ *                                   dimensions exactly as cr_propose: dim_normals (rounds,3,N,P), prior_mu / prior_sigma
+ * basis (N,P,3,3) standard normals -> the orientation (randn_orthobasis_torch, utils.py:62-69: rows normalised, row0 =
+ * normalise(row1 x row2), row1 = normalise(row2 x row0)).  boxes (N,4); img_idx (N) int32 into depth (B,H,W) and K (B,3,3);
+ * P in [2,1024].  Pointers the mode does not read may be NULL.  out_cubes (N,P,15) = x y z w h l, R row-major;
+ * out_exhausted (1) int32 is cleared by the entry and counts the ROTATION entries still outside their range after `rounds`.
+ * CR_SAMPLER_Z: a patch that holds a NaN gives NaN z for its object as torch.quantile does; an EMPTY patch, where the
+ * reference raises, gives NaN z for that object too -- the launch itself succeeds (CR_OK). */
+#define CR_SAMPLER_RANDOM 0
+#define CR_SAMPLER_XY 1
+#define CR_SAMPLER_Z 2
+#define CR_SAMPLER_DIM 3
+#define CR_SAMPLER_ASPECT 4
+#define CR_SAMPLER_ROTATION 5
+int cr_propose_sampler_batched(cr_ctx* ctx, int mode, const float* boxes, const int32_t* img_idx, int64_t N,
+                               const float* depth, int B, int H, int W, const float* prior_mu, const float* prior_sigma,
+                               const float* K, float im_w, float im_h, int64_t P, const float* uniforms,
+                               const float* ctr_normals, const float* dim_normals, int rounds, const int32_t* ratio_idx,
+                               const float* basis, float* out_cubes, int32_t* out_exhausted);
+
 /* K21: Plane.fit_parallel -- ProposalNetwork/utils/plane.py:79-134 with the
  * sampled index triples given.  pts (Q,3); triples (T,3) int32;
  * out_neg_eq (4) = -(a,b,c,d) as the reference returns; out_counts (T) int32

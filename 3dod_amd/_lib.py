@@ -161,6 +161,8 @@ SIGNATURES = {
                                  c_int, c_int, P, P, P],
     "cr_cube_decode_infer_param": [P, P, c_int, P, c_int, P, P, P, P, P, c_int, c_int, P, c_int, c_int, P, P, c_int, c_int, P],
     "cr_box3d_overlap": [P, P, P, c_int, c_int, P, P],
+    "cr_eval_iou_groups": [P, c_int, c_int, P, P, P, c_int64, P, P, P, P, ctypes.c_double, P, P, P],
+    "cr_eval_match_groups": [P, c_int, P, P, P, P, P, P, P, P, P, P, c_int, P, P, P, P],
     "cr_nonfinite_flag": [P, P, c_int64, P],
     "cr_sgd_step": [P, P, P, P, c_int64, c_float, P, c_float, c_float, c_float, P],
     "cr_sgd_step_nesterov": [P, P, P, P, c_int64, c_float, P, c_float, c_float, c_float, P],

@@ -23,8 +23,9 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno
 # dense_train.hip: two kernels must reproduce the same IoU bits (equality test of allow_low_quality_matches).
 # weak.hip: the hull march compares float32 cross products for exact ties like the reference's tensor arithmetic.
 # propose_samplers.hip: like geometry.hip, the float32 op order of the samplers is part of the parity with the reference.
+# eval.hip: the float64 2D IoU of the evaluation kernels is bit-equal to the host's numpy iou_xywh.
 EXTRA = {"geometry.hip": ["-ffp-contract=off"], "dense_train.hip": ["-ffp-contract=off"], "weak.hip": ["-ffp-contract=off"],
-         "propose_samplers.hip": ["-ffp-contract=off"]}
+         "propose_samplers.hip": ["-ffp-contract=off"], "eval.hip": ["-ffp-contract=off"]}
 
 
 def _newer(a, b):

@@ -15,7 +15,9 @@ EXTRA_DEFAULTS = {
     "DATALOADER": {"BALANCE_DATASETS": False},
     "INPUT": {"RANDOM_FLIP": "horizontal"},
     "SOLVER": {"TYPE": "sgd"},
-    "TEST": {"DETECTIONS_PER_IMAGE": 100, "VISIBILITY_THRES": 0.5, "TRUNCATION_THRES": 0.5},
+    # EVAL_BACKEND (not a key of the reference): "host" scores detections per (image, category) in Python, "device" in two
+    # batched HIP launches (3dod_amd/evalops.py)
+    "TEST": {"DETECTIONS_PER_IMAGE": 100, "VISIBILITY_THRES": 0.5, "TRUNCATION_THRES": 0.5, "EVAL_BACKEND": "host"},
     "MODEL": {
         "USE_BN": True, "STABILIZE": 0.01, "WEIGHTS_PRETRAIN": "", "DEPTH_ON": False,
         "RPN": {"IGNORE_THRESHOLD": 0.5, "OBJECTNESS_UNCERTAINTY": "IoUness"},

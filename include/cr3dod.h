@@ -937,6 +937,34 @@ int cr_cube_decode_infer_param(cr_ctx* ctx, const float* raw, int ld, const int*
  * boxes1 (N,8,3), boxes2 (M,8,3) f32 corners in pytorch3d's order -> vol (N,M), iou (N,M). */
 int cr_box3d_overlap(cr_ctx* ctx, const float* boxes1, const float* boxes2, int N, int M, float* vol, float* iou);
 
+/* ---- AP2D / AP3D evaluation of a whole dataset (omni3d_evaluation.py computeIoU :1360-1432, evaluateImg :1434-1553) ----
+ * A group is one (image, category) pair with a detection or a ground-truth box.  dt_off / gt_off (n_groups + 1) int32 index
+ * the packed detection / ground-truth arrays (detections sorted by descending score, cut to maxDets[-1]); the IoU matrix of
+ * group g is row-major D_g x G_g at iou_off[g] (n_groups + 1 int64, iou_off[n_groups] = n_pairs).  All pointers are caller-owned
+ * device memory; both calls enqueue on the context's stream and do not synchronise.
+ * cr_eval_iou_groups: one thread per pair.  mode3d 0: float64 IoU of dt_bbox / gt_bbox ([x,y,w,h] f64), bit-equal to the host's
+ *   iou_xywh.  mode3d 1: the IoU3D of cr_box3d_overlap's algorithm on dt_box3d / gt_box3d ((.,8,3) f32), widened to f64.
+ *   prox (n_pairs bytes) or NULL: 1 where the f64 2D IoU of the bbox fields is > prox_thresh.  nonfinite (n_groups int32): set
+ *   to 1 for a group with an IoU that is NaN or infinite, 0 otherwise. */
+int cr_eval_iou_groups(cr_ctx* ctx, int mode3d, int n_groups, const int* dt_off, const int* gt_off, const int64_t* iou_off,
+                       int64_t n_pairs, const double* dt_bbox, const double* gt_bbox, const float* dt_box3d,
+                       const float* gt_box3d, double prox_thresh, double* iou, unsigned char* prox, int* nonfinite);
+/* cr_eval_match_groups: the greedy matching of evaluateImg for every (group, range a of the 4, threshold t of the T), one wave
+ *   per (group, range).  Ground truth gi is ignored for range a when gt_flag is set or gt_val (area / depth) is outside
+ *   [rng[2a], rng[2a+1]].  Detection d takes, among the ground truths not yet matched at t (and in proximity, when prox is
+ *   given) with iou >= min(thrs[t], 1 - 1e-10), the real one of maximum IoU, else the ignored one of maximum IoU; equal IoUs go
+ *   to the larger index.  Outputs of group g (D detections, G ground truths, original ground-truth order), range a:
+ *     match     int32 at (4 dt_off[g] + a D) T, [T][D]: ground-truth index within the group or -1
+ *     dt_ignore uint8, same layout: matched to an ignored ground truth; or unmatched and dt_val outside the range or (with
+ *               prox and G > 0) in proximity of no ground truth
+ *     gt_ignore uint8 at 4 gt_off[g] + a G, [G]
+ *     gt_match  int32 at (4 gt_off[g] + a G) T, [T][G]: the detection matched to the ground truth or -1 (the scan's state)
+ *   No atomics: the same inputs give the same bits. */
+int cr_eval_match_groups(cr_ctx* ctx, int n_groups, const int* dt_off, const int* gt_off, const int64_t* iou_off,
+                         const double* iou, const unsigned char* prox, const double* dt_val, const double* gt_val,
+                         const unsigned char* gt_flag, const double* rng, const double* thrs, int T, int* match,
+                         unsigned char* dt_ignore, unsigned char* gt_ignore, int* gt_match);
+
 /* ---- optimizer (tools/train_net.py:233-266, cubercnn/solver/build.py:50-56) ------------- */
 int cr_nonfinite_flag(cr_ctx* ctx, const float* g, int64_t n, int* flag);
 /* SGD momentum on flat f32 buffers; skipped on device when *skip_flag != 0 (may be NULL).  The learning rate is

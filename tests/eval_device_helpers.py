@@ -1,0 +1,85 @@
+"""Shared by tests/test_eval_pack.py (CPU) and tests/test_gpu_eval_device.py (GPU): record builders and the host route
+(Omni3Deval._evaluate_img) driven with given IoU / proximity matrices, per group of a packed evaluation."""
+import importlib
+
+import numpy as np
+
+from tests.test_iou3d import box, rot
+
+ev_mod = importlib.import_module("3dod_amd.cubercnn.evaluation.omni3d_evaluation")
+evalops = importlib.import_module("3dod_amd.evalops")
+
+
+def cuboid(rng, centre=(0.0, 0.0, 8.0), spread=1.0):
+    """a random oriented cuboid near `centre`: (8,3) corners"""
+    return box(np.asarray(centre) + rng.normal(size=3) * spread, rng.uniform(0.6, 2.5, 3), rot(rng.normal(size=3), rng.uniform(0, 3)))
+
+
+def gt_rec(img, cat, idx, corners, bbox, depth, area, ignore=0):
+    return {"image_id": img, "category_id": cat, "id": idx, "bbox": [float(v) for v in bbox], "area": float(area),
+            "bbox3D": np.asarray(corners).tolist(), "depth": float(depth), "ignore2D": int(ignore), "ignore3D": int(ignore)}
+
+
+def dt_rec(img, cat, corners, bbox, depth, area, score):
+    return {"image_id": img, "category_id": cat, "bbox": [float(v) for v in bbox], "area": float(area),
+            "bbox3D": np.asarray(corners).tolist(), "depth": float(depth), "score": float(score)}
+
+
+def sorted_dets(ev, img, cat):
+    """the host's order: stable descending score, cut to maxDets[-1] (Omni3Deval._ious)"""
+    dt = ev._dts[img, cat]
+    order = np.argsort([-d["score"] for d in dt], kind="mergesort")[:ev.params.maxDets[-1]]
+    return [dt[i] for i in order]
+
+
+def host_eval_imgs(ev, packed, iou=None, prox=None):
+    """evalImgs of the host's _evaluate_img for every group of `packed`.  iou / prox: flat per-pair arrays in the packed layout
+    (group g row-major D x G at iou_off[g]) to score with; None: the host's own _ious."""
+    p = ev.params
+    out = {(cat, a, img): None for cat in p.catIds for a in range(len(p.areaRng)) for img in p.imgIds}
+    for g in range(packed["n_groups"]):
+        cat, img = packed["grp_cat"][g], packed["grp_img"][g]
+        if iou is None:
+            dts, m, px = ev._ious(img, cat)
+        else:
+            dts = sorted_dets(ev, img, cat)
+            D, G, o = len(dts), len(ev._gts[img, cat]), int(packed["iou_off"][g])
+            assert D == packed["dt_off"][g + 1] - packed["dt_off"][g] and G == packed["gt_off"][g + 1] - packed["gt_off"][g]
+            m = np.asarray(iou[o:o + D * G], dtype=np.float64).reshape(D, G)
+            px = np.asarray(prox[o:o + D * G]).astype(bool).reshape(D, G) if (prox is not None and D and G) else None
+        for a, rng in enumerate(p.areaRng):
+            out[cat, a, img] = ev._evaluate_img(img, cat, rng, p.maxDets[-1], dts, m, px)
+    return out
+
+
+def kernel_outputs_from_host(ev, packed, eval_imgs):
+    """the host's per-group results written into the kernels' output layout (3dod_amd/evalops.py docstring)"""
+    p = ev.params
+    T = len(p.iouThrs)
+    f_rng, f_ign = ("depth", "ignore3D") if ev.mode == "3D" else ("area", "ignore2D")
+    match, dt_ig, gt_ig = [], [], []
+    for g in range(packed["n_groups"]):
+        cat, img = packed["grp_cat"][g], packed["grp_img"][g]
+        gts = ev._gts[img, cat]
+        index_of = {float(x["id"]): i for i, x in enumerate(gts)}
+        for a, rng in enumerate(p.areaRng):
+            e = eval_imgs[cat, a, img]
+            match.append(np.array([[index_of[v] if v != 0 else -1 for v in row] for row in e["dtMatches"]], dtype=np.int32).reshape(-1))
+            dt_ig.append(e["dtIgnore"].astype(np.uint8).reshape(-1))
+        for a, rng in enumerate(p.areaRng):
+            gt_ig.append(np.array([bool(x.get(f_ign, 0)) or x[f_rng] < rng[0] or x[f_rng] > rng[1] for x in gts], dtype=np.uint8))
+    cat_ = lambda parts, dt: np.concatenate(parts).astype(dt) if parts else np.zeros(0, dt)
+    return {"match": cat_(match, np.int32), "dt_ignore": cat_(dt_ig, np.uint8), "gt_ignore": cat_(gt_ig, np.uint8),
+            "nonfinite": np.zeros(packed["n_groups"], np.int32)}
+
+
+def assert_same_eval_imgs(got, want):
+    assert set(got) == set(want)
+    for k in want:
+        if want[k] is None:
+            assert got[k] is None, k
+            continue
+        assert got[k] is not None, k
+        for f in ("dtMatches", "dtIgnore", "gtIgnore", "dtScores"):
+            assert got[k][f].shape == want[k][f].shape and np.array_equal(got[k][f], want[k][f]), (k, f, got[k][f], want[k][f])
+        assert got[k]["dtMatches"].dtype == np.float64 and got[k]["dtIgnore"].dtype == bool and got[k]["gtIgnore"].dtype == np.int64

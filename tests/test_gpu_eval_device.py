@@ -1,0 +1,366 @@
+"""GPU: the evaluator's device backend (csrc/eval.hip through 3dod_amd/evalops.py, Omni3Deval(backend="device")).
+  1. grouped 2D IoU: bit-equal to the host's iou_xywh;
+  2. grouped 3D IoU: within 2e-4 of the float64 oracle (the bound cr_box3d_overlap is held to);
+  3. matching: the host's _evaluate_img, fed the device route's own IoU / proximity matrices, gives exactly the same evalImgs;
+  4. end to end: precision / recall / stats exactly equal to the host route on the same IoU bits, the hand-computed fixtures of
+     tests/test_evaluation.py, and within 1e-3 of the default host route (cr_box3d_overlap per group);
+  5. groups with a non-finite IoU fall back to the host route, the others never call _evaluate_img;
+  6. Omni3DEvaluationHelper(backend="device") on a two-split dataset, pooled row included;
+  7. two runs return identical arrays."""
+import copy
+import importlib
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import iou3d as O
+from tests import eval_device_helpers as H
+from tests.test_evaluation import rec
+
+pytestmark = pytest.mark.gpu
+ev_mod, evalops = H.ev_mod, H.evalops
+DEV = torch.device("cuda:0")
+
+DEPTHS = [0.0, 5.0, 10.0, 20.0, 35.0, 50.0, 1e5, 2e5, -1.0]             # both edges of every 3D range; the last two lie outside all
+AREAS = [0.0, 500.0, 32.0 ** 2, 5000.0, 96.0 ** 2, 20000.0, 1e10, 2e10, -1.0]
+
+
+def device_route(ev):
+    """what Omni3Deval._evaluate_device does, keeping the device tensors"""
+    p = ev.params
+    packed = evalops.pack(ev)
+    out = evalops.run(packed, p.areaRng, p.iouThrs, eval_prox=ev.eval_prox, prox_thresh=p.proximity_thresh, keep_device=True)
+    evalops.unpack(ev, packed, out)
+    return packed, out
+
+
+def grouped_iou3d(d, g):
+    """the grouped kernel called on one group: the iou3d_fn hook of the host route"""
+    d = torch.as_tensor(np.asarray(d), dtype=torch.float32, device=DEV).reshape(-1, 8, 3)
+    g = torch.as_tensor(np.asarray(g), dtype=torch.float32, device=DEV).reshape(-1, 8, 3)
+    D, G = d.shape[0], g.shape[0]
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=DEV)
+    iou, _, flag = evalops.eval_iou_groups(True, i32([0, D]), i32([0, G]), torch.tensor([0, D * G], device=DEV), D * G, None,
+                                           None, d, g, 0.3, False)
+    return iou.cpu().numpy().reshape(D, G)
+
+
+def group_records(rng, img, cat, G, D, gts, dts, extra_raw=0):
+    """one (image, category) group: G ground truths (duplicates, ignore flags, range values on the edges), D detections that
+    are jittered or exact copies of ground truths (or random), some with range values outside every range"""
+    boxes, corners = [], []
+    for k in range(G):
+        if k in (1, 3) and G > k:                                        # exact duplicates: equal IoUs, the last index wins
+            boxes.append(list(boxes[k - 1])), corners.append(corners[k - 1].copy())
+        else:
+            boxes.append([rng.uniform(0, 30), rng.uniform(0, 30), rng.uniform(20, 40), rng.uniform(20, 40)])
+            corners.append(H.cuboid(rng, spread=0.7))
+    for k in range(G):
+        ign = (k in (2, 3) and G >= 6) or rng.random() < 0.15            # 2 and 3: a tie inside the ignored tier
+        gts.append(H.gt_rec(img, cat, len(gts) + 1, corners[k], boxes[k], rng.choice(DEPTHS[:7] if k < 4 else DEPTHS),
+                            rng.choice(AREAS[:7] if k < 4 else AREAS), ignore=ign))
+    for k in range(D + extra_raw):
+        if G and k % 3:
+            j = int(rng.integers(0, G))
+            exact = rng.random() < 0.3
+            b = [v + (0 if exact else rng.normal() * 2) for v in boxes[j]]
+            c = corners[j] + (0 if exact else rng.normal(size=3) * 0.15)
+        else:
+            b = [rng.uniform(0, 30), rng.uniform(0, 30), rng.uniform(20, 40), rng.uniform(20, 40)]
+            c = H.cuboid(rng, spread=0.7)
+        dts.append(H.dt_rec(img, cat, c, b, rng.choice(DEPTHS), rng.choice(AREAS), round(float(rng.random()), 1)))   # tied scores
+
+
+@pytest.fixture(scope="module")
+def match_records():
+    rng = np.random.default_rng(21)
+    gts, dts, img = [], [], 0
+    for G in (0, 1, 63, 64, 65, 130):
+        for D in (0, 1, 100):
+            if G or D:
+                img += 1
+                group_records(rng, img, 0, G, D, gts, dts)
+    group_records(rng, 500, 0, 5, 100, gts, dts, extra_raw=1)             # 101 raw detections: the cut to maxDets[-1]
+    # image 900: two identical detections on a real and an ignored copy of one box -- the second detection finds the real
+    # ground truth taken and matches the ignored one
+    c, b = H.cuboid(rng), [10.0, 10.0, 30.0, 30.0]
+    gts.append(H.gt_rec(900, 0, len(gts) + 1, c, b, 20.0, 5000.0, ignore=0))
+    gts.append(H.gt_rec(900, 0, len(gts) + 1, c, b, 20.0, 5000.0, ignore=1))
+    dts.append(H.dt_rec(900, 0, c, b, 20.0, 5000.0, 0.9))
+    dts.append(H.dt_rec(900, 0, c, b, 20.0, 5000.0, 0.8))
+    return gts, dts
+
+
+def random_dataset(seed, n_img=40, n_cat=3):
+    rng = np.random.default_rng(seed)
+    gts, dts = [], []
+    for img in range(n_img):
+        for cat in range(n_cat):
+            for _ in range(int(rng.integers(0, 4))):
+                ctr = rng.normal(size=3) * [3, 1, 0.5] + [0, 0, rng.choice([6.0, 20.0, 50.0])]
+                dims, R = rng.uniform(0.6, 2.5, 3), H.rot([0, 1, 0], rng.uniform(0, 3))
+                b = [rng.uniform(0, 400), rng.uniform(0, 300), rng.uniform(10, 150), rng.uniform(10, 150)]
+                gts.append(H.gt_rec(img, cat, len(gts) + 1, H.box(ctr, dims, R), b, ctr[2], b[2] * b[3], ignore=rng.random() < 0.1))
+                for j in range(int(rng.integers(0, 3))):                  # a good and a sloppy detection
+                    c2 = H.box(ctr + rng.normal(size=3) * (0.1 + 0.4 * j), dims * rng.uniform(0.8, 1.2, 3), R @ H.rot([0, 1, 0], rng.normal() * 0.2))
+                    b2 = [v + rng.normal() * (2 + 6 * j) for v in b]
+                    dts.append(H.dt_rec(img, cat, c2, b2, ctr[2], max(b2[2], 0) * max(b2[3], 0), rng.random()))
+            if rng.random() < 0.3:                                        # a false positive
+                b = [rng.uniform(0, 400), rng.uniform(0, 300), rng.uniform(10, 150), rng.uniform(10, 150)]
+                dts.append(H.dt_rec(img, cat, H.cuboid(rng, (0, 0, 20.0), 3.0), b, 20.0, b[2] * b[3], rng.random()))
+    return gts, dts
+
+
+# ---------------------------------------------------------------------------------------------------------------- 1, 2: the IoUs
+def test_grouped_iou2d_is_bit_equal_to_iou_xywh():
+    rng = np.random.default_rng(3)
+    gts, dts = [], []
+    rb = lambda: [rng.uniform(0, 50) / 3, rng.uniform(0, 50) / 7, rng.uniform(5, 60) / 3, rng.uniform(5, 60) / 7]
+    unit = np.zeros((8, 3))
+    sizes = [(3, 2), (1, 1), (4, 5), (2, 0), (0, 3), (7, 9)]
+    for img, (D, G) in enumerate(sizes):
+        gb = [rb() for _ in range(G)]
+        db = [rb() for _ in range(D)]
+        if img == 0:
+            gb[0][2] = 0.0                      # zero-area ground truth
+            db[0] = [0.0, 0.0, 0.0, 0.0]        # zero-area detection: union 0 with nothing, IoU 0
+            db[1] = list(gb[1])                 # identical boxes
+            db[2] = [500.0, 500.0, 3.0, 3.0]    # disjoint
+        if img == 2:
+            gb[4] = [0.0, 0.0, 0.0, 0.0]
+            db[3] = [0.0, 0.0, 0.0, 0.0]        # both empty: union 0 -> 0, not 0/0
+            db[0] = [gb[0][0] + gb[0][2], gb[0][1], 4.0, 4.0]             # touching edge: zero-width intersection
+        for k in range(G):
+            gts.append(H.gt_rec(img, 0, len(gts) + 1, unit, gb[k], 5.0, 100.0))
+        for k in range(D):
+            dts.append(H.dt_rec(img, 0, unit, db[k], 5.0, 100.0, 1.0 - 0.01 * k))
+    ev = ev_mod.Omni3Deval(gts, dts, "2D", backend="device")
+    packed, out = device_route(ev)
+    assert packed["n_groups"] == 6 and not out["nonfinite"].any()
+    got = out["iou"].cpu().numpy()
+    n_pos = 0
+    for g, (D, G) in enumerate(sizes):
+        d0, g0, o = packed["dt_off"][g], packed["gt_off"][g], packed["iou_off"][g]
+        want = ev_mod.iou_xywh(packed["dt_bbox"][d0:d0 + D], packed["gt_bbox"][g0:g0 + G]).reshape(-1)
+        assert np.array_equal(got[o:o + D * G].view(np.int64), want.view(np.int64)), (g, got[o:o + D * G], want)
+        n_pos += int(((want > 0) & (want < 1)).sum())
+    assert n_pos > 20 and (got == 1.0).any() and (got == 0.0).any()
+
+
+def test_grouped_iou3d_against_the_float64_oracle():
+    rng = np.random.default_rng(5)
+    sizes = [(1, 1), (3, 0), (0, 2), (5, 7), (100, 65)]
+    gts, dts = [], []
+    for img, (D, G) in enumerate(sizes):
+        gc = [H.cuboid(rng, spread=0.9) for _ in range(G)]
+        for k in range(G):
+            gts.append(H.gt_rec(img, 0, len(gts) + 1, gc[k], [0, 0, 10, 10], 8.0, 100.0))
+        for k in range(D):
+            c = gc[k % G] + rng.normal(size=3) * 0.3 if (G and k % 2) else H.cuboid(rng, spread=0.9)
+            dts.append(H.dt_rec(img, 0, c, [0, 0, 10, 10], 8.0, 100.0, 1.0 - 0.001 * k))
+    ev = ev_mod.Omni3Deval(gts, dts, "3D", backend="device")
+    packed, out = device_route(ev)
+    got = out["iou"].cpu().numpy()
+    assert len(got) == 1 + 35 + 6500 and not out["nonfinite"].any()
+    worst, n_pos, n_zero = 0.0, 0, 0
+    for g, (D, G) in enumerate(sizes):
+        if D * G == 0:
+            assert packed["iou_off"][g + 1] == packed["iou_off"][g]
+            continue
+        d0, g0, o = packed["dt_off"][g], packed["gt_off"][g], packed["iou_off"][g]
+        want = O.box3d_overlap(packed["dt_box3d"][d0:d0 + D].astype(np.float64), packed["gt_box3d"][g0:g0 + G].astype(np.float64))[1]
+        worst = max(worst, float(np.abs(got[o:o + D * G].reshape(D, G) - want).max()))
+        n_pos, n_zero = n_pos + int((want > 0.05).sum()), n_zero + int((want == 0).sum())
+    print("grouped IoU3D: max |kernel - float64 oracle| = %.3g over %d pairs" % (worst, len(got)))
+    assert worst < 2e-4, worst
+    assert n_pos > 100 and n_zero > 20                                    # both regimes covered
+
+
+# ---------------------------------------------------------------------------------------------------------------- 3: matching
+@pytest.mark.parametrize("mode,prox", [("2D", False), ("2D", True), ("3D", False), ("3D", True)])
+def test_matching_equals_the_host_scan_on_the_same_ious(match_records, mode, prox):
+    gts, dts = match_records
+    ev = ev_mod.Omni3Deval(gts, dts, mode, eval_prox=prox, backend="device")
+    packed, out = device_route(ev)
+    assert not out["nonfinite"].any()
+    g500 = packed["grp_img"].index(500)
+    assert packed["dt_off"][g500 + 1] - packed["dt_off"][g500] == 100    # 101 raw detections, cut
+    iou = out["iou"].cpu().numpy()
+    px = out["prox"].cpu().numpy() if prox else None
+    assert (out["prox"] is None) == (not prox)
+    host = ev_mod.Omni3Deval(gts, dts, mode, eval_prox=prox)
+    want = H.host_eval_imgs(host, packed, iou, px)
+    H.assert_same_eval_imgs(ev.evalImgs, want)
+    # the case spelled out: on image 900 the second detection matches the ignored copy because the real one is taken
+    g = packed["grp_img"].index(900)
+    T, d0, g0 = len(ev.params.iouThrs), int(packed["dt_off"][g]), int(packed["gt_off"][g])
+    m = out["match"][4 * T * d0:4 * T * (d0 + 2)].reshape(4, T, 2)
+    di = out["dt_ignore"][4 * T * d0:4 * T * (d0 + 2)].reshape(4, T, 2)
+    assert (m[0, :, 0] == 0).all() and (m[0, :, 1] == 1).all() and not di[0, :, 0].any() and di[0, :, 1].all()
+    assert out["gt_ignore"][4 * g0:4 * g0 + 2].tolist() == [0, 1]
+    gm = out["gt_match"].cpu().numpy()[4 * T * g0:4 * T * (g0 + 2)].reshape(4, T, 2)
+    assert (gm[0, :, 0] == 0).all() and (gm[0, :, 1] == 1).all()
+    # the fixture exercises what it is meant to: matches to real and to ignored ground truth, unmatched detections, ties
+    allm = np.concatenate([e["dtMatches"].reshape(-1) for e in want.values() if e is not None])
+    alli = np.concatenate([e["dtIgnore"].reshape(-1) for e in want.values() if e is not None])
+    assert ((allm != 0) & ~alli).sum() > 100 and ((allm != 0) & alli).sum() > 100 and ((allm == 0) & alli).sum() > 100
+    assert ((allm == 0) & ~alli).sum() > 100
+
+
+# ---------------------------------------------------------------------------------------------------------------- 4: end to end
+@pytest.mark.parametrize("mode", ["2D", "3D"])
+def test_end_to_end_equals_the_host_route_on_the_same_iou_bits(mode):
+    gts, dts = random_dataset(7)
+    dev = ev_mod.Omni3Deval(gts, dts, mode, backend="device")
+    a = dev.evaluate().accumulate().summarize()
+    host = ev_mod.Omni3Deval(gts, dts, mode, backend="host", iou3d_fn=grouped_iou3d)
+    b = host.evaluate().accumulate().summarize()
+    H.assert_same_eval_imgs(dev.evalImgs, host.evalImgs)
+    assert np.array_equal(dev.eval["precision"], host.eval["precision"]) and np.array_equal(dev.eval["recall"], host.eval["recall"])
+    assert np.array_equal(a, b), (a, b)
+    assert 0.05 < a[0] < 0.95 and (a[4:7] > -1).all(), a                 # a non-trivial AP, every range populated
+    assert set(dev.device_ms) == {"iou", "match"}
+    if mode == "3D":
+        c = ev_mod.Omni3Deval(gts, dts, "3D").evaluate().accumulate().summarize()        # cr_box3d_overlap per group
+        assert np.abs(a - c).max() < 1e-3, (a, c)
+
+
+def test_hand_computed_fixtures_through_the_device_backend():
+    """the three closed-loop cases of tests/test_evaluation.py with the same expected numbers"""
+    D = lambda gts, dts, mode: ev_mod.Omni3Deval(gts, dts, mode, backend="device").evaluate().accumulate()
+    gts = [rec(1, 0, 1, [0, 0, 5], [1, 1, 1]), rec(2, 0, 2, [1, 0, 6], [1, 2, 1])]
+    dts = [rec(1, 0, 1, [0, 0, 5], [1, 1, 1], score=0.9), rec(1, 0, 2, [3, 3, 5], [1, 1, 1], score=0.8),
+           rec(2, 0, 3, [1, 0, 6], [1, 2, 1], score=0.7)]
+    want = (51 * 1.0 + 50 * 2.0 / 3.0) / 101
+    for mode in ("2D", "3D"):
+        s = D(gts, dts, mode).summarize()
+        assert abs(s[0] - want) < 1e-9 and abs(s[1] - want) < 1e-9, (mode, s)
+        assert abs(s[9] - 1.0) < 1e-12 and abs(s[7] - 1.0) < 1e-12
+    assert abs(s[4] - want) < 1e-9 and s[5] == -1 and s[6] == -1
+
+    gts = [rec(1, 0, 1, [0, 0, 20], [2, 2, 2])]
+    dts = [rec(1, 0, 1, [1, 0, 20], [2, 2, 2], score=0.5)]
+    e = D(gts, dts, "3D")
+    s = e.summarize()
+    n_tp = int((e.params.iouThrs <= 1 / 3 + 1e-12).sum())
+    assert n_tp == 6 and abs(s[0] - n_tp / 10) < 1e-9
+    assert abs(s[1] - 1.0) < 1e-9 and abs(s[2] - 1.0) < 1e-9 and abs(s[3] - 0.0) < 1e-9
+    assert s[4] == -1 and abs(s[5] - n_tp / 10) < 1e-9 and s[6] == -1
+    gts[0]["ignore3D"] = 1
+    assert D(gts, dts, "3D").summarize()[0] == -1
+    gts.append(rec(1, 0, 2, [8, 0, 20], [2, 2, 2]))
+    dts.append(rec(1, 0, 2, [8, 0, 20], [2, 2, 2], score=0.4))
+    assert abs(D(gts, dts, "3D").summarize()[0] - (6 * 1.0 + 4 * 0.5) / 10) < 1e-9
+
+    gts = [rec(1, c, c + 1, [3 * c, 0, 5], [1, 1, 1]) for c in range(3)]
+    dts = [rec(1, c, c + 1, [3 * c, 0, 5], [1, 1, 1], score=0.9 - 0.1 * c) for c in range(2)]
+    s = D(gts, dts, "3D").summarize()
+    assert abs(s[0] - 2 / 3) < 1e-9 and abs(s[9] - 2 / 3) < 1e-9
+
+
+# ---------------------------------------------------------------------------------------------------------------- 5: fallback
+def test_nonfinite_groups_fall_back_to_the_host_route():
+    """image 0 / category 0 holds a ground-truth box of zero volume and a detection of zero volume: their IoU is 0/0.  (A
+    zero-volume box against a proper one gives 0 / volume = 0, which is finite and needs no fallback.)"""
+    gts, dts = random_dataset(9, n_img=6)
+    point = np.tile([[0.5, 0.2, 6.0]], (8, 1))
+    gts.append(H.gt_rec(0, 0, len(gts) + 1, point, [5, 5, 20, 20], 6.0, 400.0))
+    dts.append(H.dt_rec(0, 0, point, [5, 5, 20, 20], 6.0, 400.0, 0.95))
+    dev = ev_mod.Omni3Deval(gts, dts, "3D", backend="device")
+    calls, inner = [], dev._evaluate_img
+    dev._evaluate_img = lambda img, cat, *a: calls.append((img, cat)) or inner(img, cat, *a)
+    packed, out = device_route(dev)
+    flagged = [(packed["grp_img"][g], packed["grp_cat"][g]) for g in np.nonzero(out["nonfinite"])[0]]
+    assert flagged == [(0, 0)]
+    assert np.isnan(out["iou"].cpu().numpy()).sum() == 1
+    assert set(calls) == {(0, 0)} and len(calls) == 4                     # no other group went through the host scan
+    host_default = ev_mod.Omni3Deval(gts, dts, "3D").evaluate()          # the flagged group: the host route as it is
+    host_same = ev_mod.Omni3Deval(gts, dts, "3D", iou3d_fn=grouped_iou3d).evaluate()
+    keys0 = [k for k in dev.evalImgs if (k[2], k[0]) == (0, 0)]
+    assert len(keys0) == 4
+    H.assert_same_eval_imgs({k: dev.evalImgs[k] for k in keys0}, {k: host_default.evalImgs[k] for k in keys0})
+    rest = [k for k in dev.evalImgs if (k[2], k[0]) != (0, 0)]
+    H.assert_same_eval_imgs({k: dev.evalImgs[k] for k in rest}, {k: host_same.evalImgs[k] for k in rest})
+    # through the public route
+    again = ev_mod.Omni3Deval(gts, dts, "3D", backend="device").evaluate()
+    H.assert_same_eval_imgs(again.evalImgs, dev.evalImgs)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 6: the helper
+def test_helper_with_device_backend_on_two_splits(tmp_path, monkeypatch):
+    syn = importlib.import_module("3dod_amd.synthetic")
+    data = importlib.import_module("3dod_amd.cubercnn.data")
+    Dm = importlib.import_module("3dod_amd.d2lite.data")
+    root = tmp_path / "datasets"
+    root.mkdir()
+    names = ["Synth_val", "Synth_SUNRGBD_val"]                            # the second name turns eval_prox on
+    syn.make_omni3d_dataset(str(root), name=names[0], n_images=8, seed=11)
+    syn.make_omni3d_dataset(str(root), name=names[1], n_images=6, seed=12, first_image_id=3000)
+    monkeypatch.chdir(tmp_path)
+    for n in list(Dm.DatasetCatalog):
+        Dm.DatasetCatalog.remove(n)
+    for n in ["omni3d_model"] + names:
+        Dm.MetadataCatalog.pop(n, None)
+    cats = ["bed", "car", "chair", "sofa", "table", "truck"]
+    cfg = syn.make_cfg(overrides=["DATASETS.TEST", tuple(names), "DATASETS.CATEGORY_NAMES", cats,
+                                  "MODEL.ROI_HEADS.NUM_CLASSES", len(cats), "VIS_PERIOD", 0, "log", False])
+    fs = data.get_filter_settings_from_cfg(cfg)
+    jsons = [os.path.join("datasets", "Omni3D", n + ".json") for n in names]
+    data.register_and_store_model_metadata(data.Omni3D(jsons, copy.deepcopy(fs)), str(tmp_path), fs)
+    id_map = Dm.MetadataCatalog.get("omni3d_model").thing_dataset_id_to_contiguous_id
+
+    def predictions(name, noisy, rng):
+        api = data.Omni3D([os.path.join("datasets", "Omni3D", name + ".json")], copy.deepcopy(fs))
+        by_img = {}
+        for a in api.dataset["annotations"]:
+            inst = {"image_id": a["image_id"], "category_id": id_map[a["category_id"]], "bbox": list(a["bbox"]), "score": 0.8,
+                    "depth": a["depth"], "bbox3D": a["bbox3D"]}
+            by_img.setdefault(a["image_id"], []).append(inst)
+            if noisy:
+                for scale in (0.05, 0.3):
+                    o = copy.deepcopy(inst)
+                    o["score"] = float(rng.random())
+                    o["bbox"] = [v + rng.normal() * 40 * scale for v in o["bbox"]]
+                    o["bbox3D"] = (np.asarray(o["bbox3D"]) + rng.normal(size=3) * scale).tolist()
+                    by_img[a["image_id"]].append(o)
+        return [{"image_id": i, "K": api.imgs[i]["K"], "width": api.imgs[i]["width"], "height": api.imgs[i]["height"],
+                 "instances": v} for i, v in by_img.items()]
+
+    def run(backend, noisy):
+        rng = np.random.default_rng(4)
+        helper = ev_mod.Omni3DEvaluationHelper(names, fs, str(tmp_path / ("eval_%s_%d" % (backend, noisy))), backend=backend)
+        assert helper.evaluators[names[1]]._eval_prox and not helper.evaluators[names[0]]._eval_prox
+        for n in names:
+            helper.add_predictions(n, predictions(n, noisy, rng))
+            helper.evaluate(n)
+        analysis, _ = helper.summarize_all()
+        return helper, analysis
+
+    helper, exact = run("device", noisy=False)
+    for n in names + ["<Concat>"]:
+        assert exact[n]["AP3D"] == pytest.approx(100.0) and exact[n]["AP2D"] == pytest.approx(100.0), (n, exact[n])
+    assert helper.evaluators[names[0]].evals["3D"].backend == "device"
+    _, dev = run("device", noisy=True)
+    _, host = run("host", noisy=True)
+    assert list(dev) == list(host) == names + ["<Concat>"]
+    for n in dev:
+        assert 1.0 < host[n]["AP3D"] < 99.0, (n, host[n])
+        for k, v in host[n].items():
+            if k != "iters":
+                assert abs(dev[n][k] - v) < 1e-3 or (np.isnan(v) and np.isnan(dev[n][k])), (n, k, dev[n][k], v)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 7: repeatability
+def test_two_runs_return_identical_arrays(match_records):
+    gts, dts = match_records
+    ev = ev_mod.Omni3Deval(gts, dts, "3D", eval_prox=True, backend="device")
+    p = ev.params
+    packed = evalops.pack(ev)
+    runs = [evalops.run(packed, p.areaRng, p.iouThrs, eval_prox=True, prox_thresh=p.proximity_thresh, keep_device=True) for _ in range(2)]
+    for k in ("match", "dt_ignore", "gt_ignore", "nonfinite"):
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+    for k in ("iou", "prox", "gt_match"):
+        assert torch.equal(runs[0][k], runs[1][k]), k
+    assert np.array_equal(runs[0]["iou"].cpu().numpy().view(np.int64), runs[1]["iou"].cpu().numpy().view(np.int64))

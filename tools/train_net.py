@@ -41,7 +41,8 @@ def do_test(cfg, model, iteration='final', storage=None):
     names = list(cfg.DATASETS.TEST)
     rank0 = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
     helper = ev.Omni3DEvaluationHelper(names, fs, os.path.join(cfg.OUTPUT_DIR, "inference", f"iter_{iteration}"),
-                                       iter_label=iteration, only_2d=cfg.MODEL.ROI_CUBE_HEAD.LOSS_W_3D == 0.0) if rank0 else None
+                                       iter_label=iteration, only_2d=cfg.MODEL.ROI_CUBE_HEAD.LOSS_W_3D == 0.0,
+                                       backend=cfg.TEST.EVAL_BACKEND) if rank0 else None
     for name in names:
         if name not in D.DatasetCatalog:
             data.simple_register(name, fs, filter_empty=False)

@@ -41,6 +41,17 @@ SIGNATURES = {
     "cr_scale_residual_layernorm": [P, P, P, P, P, P, P, P, c_int64, c_int, c_float],
     "cr_scale_residual": [P, P, P, P, P, c_int64, c_int],
     "cr_resize_bilinear_ac": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int],
+    "cr_attention_fwd_lse": [P, P, P, P, c_int, c_int, c_int, c_int, c_float],
+    "cr_attention_bwd": [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float],
+    "cr_layernorm_bwd": [P, P, P, P, P, P, P, P, c_int64, c_int, c_float, c_int, c_int],
+    "cr_layernorm_f32in": [P, P, P, P, P, c_int64, c_int, c_float],
+    "cr_scale_residual_f32": [P, P, P, P, P, c_int64, c_int],
+    "cr_gelu_fwd": [P, P, P, c_int64],
+    "cr_gelu_bwd": [P, P, P, P, c_int64],
+    "cr_layerscale_bwd": [P, P, P, P, P, P, P, c_int64, c_int, c_int],
+    "cr_resize_bilinear_ac_bwd": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int],
+    "cr_depth_reduce": [P, P, P, P, P, c_int, c_int64],
+    "cr_silog_bwd": [P, P, P, P, P, P, c_int64],
     "cr_conv2d_fwd": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, c_int, c_int, P],
     "cr_conv2d_bwd_data": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
     "cr_weight_split3": [P, P, P, c_int64, c_int],

@@ -35,9 +35,11 @@ __device__ __forceinline__ u16 vf2bf(float f) {
 
 // WAVES waves per workgroup share one K/V tile; every wave owns QB blocks of 16 queries (QB = 2: each K / V^T fragment
 // fetched from LDS feeds two MFMAs).
-template <int QB, int WAVES>
+// LSE (the training variant): additionally writes the per-row log-sum-exp m + log(l) of the scaled scores, (B,H,N) f32 -- the
+// only thing the backward needs to recompute P.  The output path is untouched, so `out` is bit-identical either way.
+template <int QB, int WAVES, bool LSE>
 __global__ __launch_bounds__(64 * WAVES) void k_attention_fwd(const u16* __restrict__ qkv, u16* __restrict__ out, int B, int N,
-                                                              int H, float scale, int qtiles) {
+                                                              int H, float scale, int qtiles, float* __restrict__ lse) {
     constexpr int T = 64 * WAVES, TQ = 16 * QB * WAVES;
     __shared__ __attribute__((aligned(16))) u16 sK[ATT_TK][ATT_D + ATT_KPAD];      // [key][d]
     __shared__ __attribute__((aligned(16))) u16 sVt[ATT_D][ATT_TK + ATT_KPAD];     // [d][key]
@@ -201,6 +203,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_attention_fwd(const u16* __restr
         const int q = q0 + 16 * qb + c;
         if (q < N) {
             const float inv = 1.f / l;
+            if constexpr (LSE) {
+                if (g == 0) lse[((size_t)b * H + h) * N + q] = m_run[qb] + logf(l);
+            }
             u16* dst = out + ((size_t)b * N + q) * ((size_t)H * ATT_D) + (size_t)h * ATT_D;
 #pragma unroll
             for (int db = 0; db < 4; ++db) {
@@ -223,8 +228,23 @@ extern "C" int cr_attention_fwd(cr_ctx* ctx, const void* qkv, void* out, int B, 
     constexpr int QB = 1, WAVES = 8;
     const int qtiles = (int)cr_cdiv(N, 16 * QB * WAVES);
     CR_CHECK_ARG((int64_t)B * H * qtiles < (1ll << 31), "cr_attention_fwd: grid too large");
-    hipLaunchKernelGGL((k_attention_fwd<QB, WAVES>), dim3((unsigned)(B * H * qtiles)), dim3(64 * WAVES), 0, ctx->stream,
-                       (const u16*)qkv, (u16*)out, B, N, H, scale, qtiles);
+    hipLaunchKernelGGL((k_attention_fwd<QB, WAVES, false>), dim3((unsigned)(B * H * qtiles)), dim3(64 * WAVES), 0, ctx->stream,
+                       (const u16*)qkv, (u16*)out, B, N, H, scale, qtiles, (float*)nullptr);
+    CR_LAUNCH_CHECK();
+    return CR_OK;
+}
+
+// the same kernel body and launch shape as cr_attention_fwd, plus the log-sum-exp rows for cr_attention_bwd (vit_bwd.hip)
+extern "C" int cr_attention_fwd_lse(cr_ctx* ctx, const void* qkv, void* out, float* lse, int B, int N, int H, int D, float scale) {
+    CR_CHECK_ARG(ctx && B >= 0 && N >= 0 && H > 0, "cr_attention_fwd_lse: bad args");
+    CR_CHECK_ARG(D == ATT_D, "cr_attention_fwd_lse: head dimension %d is not built (64 only)", D);
+    if ((int64_t)B * N == 0) return CR_OK;
+    CR_CHECK_ARG(qkv && out && lse, "cr_attention_fwd_lse: NULL pointer");
+    constexpr int QB = 1, WAVES = 8;
+    const int qtiles = (int)cr_cdiv(N, 16 * QB * WAVES);
+    CR_CHECK_ARG((int64_t)B * H * qtiles < (1ll << 31), "cr_attention_fwd_lse: grid too large");
+    hipLaunchKernelGGL((k_attention_fwd<QB, WAVES, true>), dim3((unsigned)(B * H * qtiles)), dim3(64 * WAVES), 0, ctx->stream,
+                       (const u16*)qkv, (u16*)out, B, N, H, scale, qtiles, lse);
     CR_LAUNCH_CHECK();
     return CR_OK;
 }

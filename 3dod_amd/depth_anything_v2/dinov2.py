@@ -1,11 +1,17 @@
-"""DINOv2 vision transformer, forward only (reference: depth/metric_depth/depth_anything_v2/dinov2.py and
+"""DINOv2 vision transformer (reference: depth/metric_depth/depth_anything_v2/dinov2.py and
 dinov2_layers/{attention,block,mlp,layer_scale,patch_embed}.py).
 
 Tokens live as one (B*N, C) bf16 matrix from the patch embedding to the last block: the linears are hipBLASLt GEMMs on
 cached bf16 weight copies (ops.linear), attention is the MFMA flash kernel on the packed qkv output, LayerNorm /
 GELU / LayerScale+residual are one kernel each.  Parameters keep the reference's names and float32 storage, so its
-checkpoints load with load_state_dict.  Not built: training (drop path, masks), register tokens, the SwiGLU FFN of
-ViT-g."""
+checkpoints load with load_state_dict.
+
+Training (model.train() with grad enabled, as depth/metric_depth/train.py fine-tunes it): every module takes its training
+route, the same ops as torch.autograd.Functions over the backward kernels of csrc/vit_bwd.hip -- attention keeps its
+log-sum-exp rows, GELU its pre-activation, and "x + ls * branch" and the LayerNorm after it run as two kernels on a
+residual stream kept in float32 (inference rounds it to bf16 twice per block; what the GEMMs read is bf16 either way).
+In eval() mode or under no_grad nothing changes: the same kernels in the same order.  Not built: stochastic depth and
+token masks (drop_path_rate is 0 and no masks are passed in the depth model), register tokens, the SwiGLU FFN of ViT-g."""
 import math
 from functools import partial
 
@@ -14,6 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import hipops as ops
+from .util.blocks import training as _training
 
 
 class PatchEmbed(nn.Module):
@@ -61,7 +68,8 @@ class Attention(nn.Module):
 
     def forward(self, x, B, N):
         qkv = ops.linear(x, self.qkv.weight, self.qkv.bias)                        # (B*N, 3*H*D) == (B,N,3,H,D)
-        a = ops.attention(qkv, B, N, self.num_heads, self.head_dim, self.scale)
+        att = ops.attention_train if _training(self) else ops.attention
+        a = att(qkv, B, N, self.num_heads, self.head_dim, self.scale)
         return ops.linear(a, self.proj.weight, self.proj.bias)
 
 
@@ -78,6 +86,8 @@ class Mlp(nn.Module):
         self.fc2 = nn.Linear(hidden_features or in_features, out_features or in_features, bias=bias)
 
     def forward(self, x):
+        if _training(self):                 # the backward reads the pre-activation: no in-place GELU
+            return ops.linear(ops.gelu_train(ops.linear(x, self.fc1.weight, self.fc1.bias)), self.fc2.weight, self.fc2.bias)
         return ops.linear(ops.gelu_(ops.linear(x, self.fc1.weight, self.fc1.bias)), self.fc2.weight, self.fc2.bias)
 
 
@@ -100,6 +110,11 @@ class Block(nn.Module):
         follows it (the second one of this block, or the first of the next block)."""
         g1 = self.ls1.gamma if isinstance(self.ls1, LayerScale) else None
         g2 = self.ls2.gamma if isinstance(self.ls2, LayerScale) else None
+        if _training(self):
+            n1, n2 = self.norm1, self.norm2
+            x = ops.scale_residual_train(x, self.attn(ops.layernorm_train(x, n1.weight, n1.bias, n1.eps), B, N), g1)
+            x = ops.scale_residual_train(x, self.mlp(ops.layernorm_train(x, n2.weight, n2.bias, n2.eps)), g2)
+            return x, None
         if h is None:
             h = ops.layernorm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)
         x, h = ops.scale_residual_layernorm(x, self.attn(h, B, N), g1, self.norm2.weight, self.norm2.bias, self.norm2.eps)
@@ -156,19 +171,29 @@ class DinoVisionTransformer(nn.Module):
         N = self.pos_embed.shape[1] - 1
         if npatch == N and w == h:
             return self.pos_embed
-        key = (w, h, self.pos_embed._version, self.pos_embed.data_ptr())
+        if _training(self) and self.pos_embed.requires_grad:
+            return self._resized_pos(w, h)                # differentiable, never served from / stored in the cache
+        # (a flat optimizer updates through raw pointers and does not move torch's version counter: for a table it owns
+        # -- it carries a gradient sink -- the weight epoch is part of the key)
+        epoch = ops._WEIGHT_EPOCH[0] if ops.grad_sink(self.pos_embed) is not None else 0
+        key = (w, h, self.pos_embed._version, self.pos_embed.data_ptr(), epoch)
         hit = self._pos_cache.get("k") == key
         if not hit:
-            pos = self.pos_embed.float()
-            dim = pos.shape[-1]
-            w0, h0 = w // self.patch_size + self.interpolate_offset, h // self.patch_size + self.interpolate_offset
-            sqrt_N = math.sqrt(N)
-            grid = F.interpolate(pos[:, 1:].reshape(1, int(sqrt_N), int(sqrt_N), dim).permute(0, 3, 1, 2),
-                                 scale_factor=(float(w0) / sqrt_N, float(h0) / sqrt_N), mode="bicubic",
-                                 antialias=self.interpolate_antialias)
-            assert int(w0) == grid.shape[-2] and int(h0) == grid.shape[-1]
-            self._pos_cache = {"k": key, "v": torch.cat((pos[:, :1], grid.permute(0, 2, 3, 1).view(1, -1, dim)), dim=1)}
+            with torch.no_grad():
+                self._pos_cache = {"k": key, "v": self._resized_pos(w, h)}
         return self._pos_cache["v"]
+
+    def _resized_pos(self, w, h):
+        N = self.pos_embed.shape[1] - 1
+        pos = self.pos_embed.float()
+        dim = pos.shape[-1]
+        w0, h0 = w // self.patch_size + self.interpolate_offset, h // self.patch_size + self.interpolate_offset
+        sqrt_N = math.sqrt(N)
+        grid = F.interpolate(pos[:, 1:].reshape(1, int(sqrt_N), int(sqrt_N), dim).permute(0, 3, 1, 2),
+                             scale_factor=(float(w0) / sqrt_N, float(h0) / sqrt_N), mode="bicubic",
+                             antialias=self.interpolate_antialias)
+        assert int(w0) == grid.shape[-2] and int(h0) == grid.shape[-1]
+        return torch.cat((pos[:, :1], grid.permute(0, 2, 3, 1).reshape(1, -1, dim)), dim=1)
 
     def prepare_tokens(self, x):
         """dinov2.py:211-231 without masks: (B,3,H,W) float -> ((B*N, C) bf16, B, N).  The image's first spatial axis is
@@ -185,8 +210,11 @@ class DinoVisionTransformer(nn.Module):
         the class token; tensors come back as (B, N-1, C) / (B, C) bf16."""
         if not x.is_cuda:
             raise RuntimeError("3dod_amd.depth_anything_v2 runs on the GPU only (no CPU path)")
-        with torch.no_grad():
+        train = _training(self)
+        with torch.enable_grad() if train else torch.no_grad():
             tok, B, N = self.prepare_tokens(x)
+            if train:
+                tok = tok.float()           # the training route keeps the residual stream in float32 (branches stay bf16)
             take = range(len(self.blocks) - n, len(self.blocks)) if isinstance(n, int) else n
             outs = []
             h = None
@@ -197,7 +225,8 @@ class DinoVisionTransformer(nn.Module):
                     outs.append(tok)
             assert len(outs) == len(take), f"only {len(outs)} / {len(take)} blocks found"
             if norm:
-                outs = [ops.layernorm(o, self.norm.weight, self.norm.bias, self.norm.eps) for o in outs]
+                ln = ops.layernorm_train if train else ops.layernorm
+                outs = [ln(o, self.norm.weight, self.norm.bias, self.norm.eps) for o in outs]
             outs = [o.view(B, N, -1) for o in outs]
             cls = [o[:, 0] for o in outs]
             outs = [o[:, 1:] for o in outs]

@@ -1,5 +1,8 @@
-"""DPT fusion blocks, forward only, NHWC bf16 (reference: depth/metric_depth/depth_anything_v2/util/blocks.py).
-Every convolution is the library's MFMA implicit-GEMM kernel with bias / ReLU / residual fused in its epilogue."""
+"""DPT fusion blocks, NHWC bf16 (reference: depth/metric_depth/depth_anything_v2/util/blocks.py).
+Every convolution is the library's MFMA implicit-GEMM kernel with bias / ReLU / residual fused in its epilogue.  On the
+training route (module.train() with grad enabled) the convolutions are ops.conv_bias_act (autograd over the same forward
+kernel and the library's backward-data / weight-gradient kernels), the residual adds sit beside them, and the resize
+carries its gather backward."""
 import torch
 import torch.nn as nn
 
@@ -15,6 +18,16 @@ def conv(x, m, relu=False, residual=None, out_f32=False):
     wb, _ = ops.prepared_weights(w, False)
     b = m.bias.detach().float().contiguous() if m.bias is not None else None
     return ops.conv_fwd_raw(x, wb, w.shape[0], k, s, p, bias=b, residual=residual, relu=relu, out_f32=out_f32)
+
+
+def training(module):
+    """the training route: module.train() AND grad enabled; everything else is the inference path, untouched"""
+    return module.training and torch.is_grad_enabled()
+
+
+def conv_train(x, m, relu=False, out_f32=False):
+    """`conv` on the training route: gradients reach m.weight / m.bias (or their flat-gradient sinks)"""
+    return ops.conv_bias_act(x, m.weight, m.bias, stride=m.stride[0], pad=m.padding[0], relu=relu, out_f32=out_f32)
 
 
 def _make_scratch(in_shape, out_shape, groups=1, expand=False):
@@ -42,6 +55,8 @@ class ResidualConvUnit(nn.Module):
         self.conv2 = nn.Conv2d(features, features, kernel_size=3, stride=1, padding=1, bias=True)
 
     def forward(self, x):
+        if training(self):
+            return x + conv_train(conv_train(torch.relu(x), self.conv1, relu=True), self.conv2)
         return conv(conv(torch.relu(x), self.conv1, relu=True), self.conv2, residual=x)
 
 
@@ -65,5 +80,7 @@ class FeatureFusionBlock(nn.Module):
             size = (output.shape[1] * 2, output.shape[2] * 2)
         elif size is None:
             size = self.size
+        if training(self):
+            return conv_train(ops.resize_bilinear_ac_train(output.contiguous(), size), self.out_conv)
         output = ops.resize_bilinear_ac(output, size)
         return conv(output, self.out_conv)

@@ -3629,3 +3629,260 @@ def resize_bilinear_ac(x, size):
     y = torch.empty((B, Ho, Wo, C), dtype=bf16, device=x.device)
     _lib.call("cr_resize_bilinear_ac", x, y, B, h, w, Ho, Wo, C)
     return y
+
+
+# --------------------------------------------------------------------------
+# Depth-Anything-V2 training ops (csrc/vit_bwd.hip): the ops above as autograd Functions, reached only by the model's
+# training route.  Parameter gradients go to the optimizer's flat-gradient sinks when the parameters carry them
+# (grad_sink), else to param.grad.  No float atomics: two backward passes over the same inputs give the same bits.
+# --------------------------------------------------------------------------
+RED_PARTS = 128          # partial rows of the two-stage column reductions (csrc/vit_bwd.hip)
+
+
+def attention_lse(qkv, B, N, H, D, scale):
+    """ops.attention (bit-identical output, same kernel body) plus the per-row log-sum-exp (B,H,N) f32"""
+    _need_cuda(qkv, "attention input")
+    assert qkv.dtype == bf16 and qkv.is_contiguous() and qkv.shape == (B * N, 3 * H * D)
+    out = torch.empty((B * N, H * D), dtype=bf16, device=qkv.device)
+    lse = torch.empty((B, H, N), dtype=f32, device=qkv.device)
+    _lib.call("cr_attention_fwd_lse", qkv, out, lse, B, N, H, D, float(scale))
+    return out, lse
+
+
+def attention_bwd(qkv, dout, lse, B, N, H, D, scale):
+    """dqkv in the packed layout of qkv (what the qkv linear's backward consumes)"""
+    _need_cuda(qkv, "attention input")
+    assert qkv.dtype == bf16 and dout.dtype == bf16 and lse.dtype == f32
+    assert qkv.is_contiguous() and dout.is_contiguous() and lse.is_contiguous()
+    assert qkv.shape == (B * N, 3 * H * D) and dout.shape == (B * N, H * D) and lse.shape == (B, H, N)
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty((B, H, N), dtype=f32, device=qkv.device)
+    _lib.call("cr_attention_bwd", qkv, dout, lse, delta, dqkv, B, N, H, D, float(scale))
+    return dqkv
+
+
+class _Attention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, B, N, H, D, scale):
+        out, lse = attention_lse(qkv, B, N, H, D, scale)
+        ctx.save_for_backward(qkv, lse)
+        ctx.cfg = (B, N, H, D, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, lse = ctx.saved_tensors
+        return (attention_bwd(qkv, _act_cast(dout, bf16), lse, *ctx.cfg),) + (None,) * 5
+
+
+def attention_train(qkv, B, N, H, D, scale):
+    return _Attention.apply(qkv, B, N, H, D, scale)
+
+
+def _param_acc(p, n, dev):
+    """(accumulator, grad to return): the parameter's flat-gradient sink, or a zero buffer that becomes its autograd grad"""
+    sink = grad_sink(p)
+    if sink is not None:
+        return sink, None
+    z = torch.zeros((n,), dtype=f32, device=dev)
+    return z, z
+
+
+def layernorm_bwd_raw(x, dy, gamma, dgamma, dbeta, eps, accumulate):
+    """x (M,C) bf16 or float32 (the training route's residual stream); dx comes back in x's dtype.  dgamma / dbeta: f32
+    accumulators, either may be None (not wanted)"""
+    M, C = x.shape
+    assert x.dtype in (bf16, f32) and x.is_contiguous() and dy.dtype == bf16 and dy.is_contiguous()
+    dx = torch.empty_like(x)
+    part = torch.empty((RED_PARTS * 2 * C,), dtype=f32, device=x.device)
+    _lib.call("cr_layernorm_bwd", x, dy, gamma.detach().float().contiguous(), dx, dgamma, dbeta, part, M, C, float(eps),
+              int(accumulate), int(x.dtype == f32))
+    return dx
+
+
+def layernorm_f32in(x, gamma, beta, eps):
+    """LayerNorm of float32 rows -> bf16 (cr_layernorm_f32in)"""
+    _need_cuda(x, "layernorm input")
+    assert x.dtype == f32 and x.is_contiguous() and x.dim() == 2
+    y = torch.empty(x.shape, dtype=bf16, device=x.device)
+    _lib.call("cr_layernorm_f32in", x, gamma.detach().float().contiguous(), beta.detach().float().contiguous(), y, x.shape[0],
+              x.shape[1], float(eps))
+    return y
+
+
+def scale_residual_f32(x, y, gamma=None):
+    """x + gamma * y with float32 x and result, bf16 y (cr_scale_residual_f32)"""
+    _need_cuda(x, "residual input")
+    assert x.dtype == f32 and y.dtype == bf16 and x.is_contiguous() and y.is_contiguous() and x.shape == y.shape
+    out = torch.empty_like(x)
+    g = gamma.detach().float().contiguous() if gamma is not None else None
+    _lib.call("cr_scale_residual_f32", x, y, g, out, x.shape[0], x.shape[1])
+    return out
+
+
+class _LayerNorm(torch.autograd.Function):
+    """(like _Linear, the parameters ride on ctx as plain references and the backward re-reads gamma: a weight update
+    between a forward and its backward is not detected -- the training loops here update after the backward)"""
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        ctx.save_for_backward(x)
+        ctx.refs, ctx.eps = (gamma, beta), eps
+        return layernorm_f32in(x, gamma, beta, eps) if x.dtype == f32 else layernorm(x, gamma, beta, eps)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        gamma, beta = ctx.refs
+        C = x.shape[1]
+        ag, gg = _param_acc(gamma, C, x.device) if ctx.needs_input_grad[1] else (None, None)
+        ab, gb = _param_acc(beta, C, x.device) if ctx.needs_input_grad[2] else (None, None)
+        dx = layernorm_bwd_raw(x, _act_cast(dy, bf16), gamma, ag, ab, ctx.eps, accumulate=True)
+        return dx, gg, gb, None
+
+
+def layernorm_train(x, gamma, beta, eps):
+    return _LayerNorm.apply(x, gamma, beta, eps)
+
+
+def gelu_fwd_raw(x):
+    y = torch.empty_like(x)
+    _lib.call("cr_gelu_fwd", x, y, x.numel())
+    return y
+
+
+def gelu_bwd_raw(x, dy):
+    dx = torch.empty_like(x)
+    _lib.call("cr_gelu_bwd", x, dy, dx, x.numel())
+    return dx
+
+
+class _Gelu(torch.autograd.Function):
+    """exact GELU that keeps the pre-activation (the inference path's gelu_ works in place)"""
+    @staticmethod
+    def forward(ctx, x):
+        _need_cuda(x, "gelu input")
+        assert x.dtype == bf16 and x.is_contiguous()
+        ctx.save_for_backward(x)
+        return gelu_fwd_raw(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        return gelu_bwd_raw(x, _act_cast(dy, bf16))
+
+
+def gelu_train(x):
+    return _Gelu.apply(x)
+
+
+def layerscale_bwd_raw(g, y, gamma, dgamma, accumulate):
+    M, C = g.shape
+    dy = torch.empty_like(g)
+    part = torch.empty((RED_PARTS * C,), dtype=f32, device=g.device)
+    _lib.call("cr_layerscale_bwd", g, y, gamma.detach().float().contiguous(), dy, dgamma, part, M, C, int(accumulate))
+    return dy
+
+
+class _ScaleResidual(torch.autograd.Function):
+    """(gamma rides on ctx as a plain reference and is re-read in the backward, like _Linear's weight)"""
+    @staticmethod
+    def forward(ctx, x, y, gamma):
+        ctx.save_for_backward(y)
+        ctx.gamma = gamma
+        return scale_residual_f32(x, y, gamma) if x.dtype == f32 else scale_residual(x, y, gamma)
+
+    @staticmethod
+    def backward(ctx, g):
+        y, = ctx.saved_tensors
+        gamma = ctx.gamma
+        gb = _act_cast(g, bf16)                 # the branch's gradient is bf16; the stream's passes through in its own dtype
+        if gamma is None:
+            return g, gb, None
+        acc, gg = _param_acc(gamma, gamma.numel(), g.device)
+        return g, layerscale_bwd_raw(gb, y, gamma, acc, accumulate=True), gg
+
+
+def scale_residual_train(x, y, gamma=None):
+    return _ScaleResidual.apply(x, y, gamma)
+
+
+def resize_bilinear_ac_bwd_raw(dy, in_shape):
+    B, h, w, C = in_shape
+    assert dy.dtype == bf16 and dy.is_contiguous() and dy.shape[0] == B and dy.shape[3] == C
+    dx = torch.empty((B, h, w, C), dtype=bf16, device=dy.device)
+    _lib.call("cr_resize_bilinear_ac_bwd", dy, dx, B, h, w, dy.shape[1], dy.shape[2], C)
+    return dx
+
+
+class _ResizeBilinearAC(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, size):
+        ctx.in_shape = tuple(x.shape)
+        return resize_bilinear_ac(x, size)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return resize_bilinear_ac_bwd_raw(_act_cast(dy, bf16), ctx.in_shape), None
+
+
+def resize_bilinear_ac_train(x, size):
+    return _ResizeBilinearAC.apply(x, size)
+
+
+def _depth_args(pred, target, valid):
+    _need_cuda(pred, "depth prediction")
+    assert pred.shape == target.shape == valid.shape and pred.dim() == 3, "pred / target / valid are (B,H,W)"
+    assert pred.dtype == f32 and target.dtype == f32
+    v = valid.contiguous()
+    v = v.view(torch.uint8) if v.dtype == torch.bool else (v != 0).view(torch.uint8)
+    return pred.contiguous(), target.contiguous(), v
+
+
+def depth_reduce(pred, target, valid):
+    """(B,10) float64 per-image masked sums (cr_depth_reduce): count, sum dl, sum dl^2, sum |d|/t, sum d^2/t, sum d^2,
+    sum |log10 p - log10 t|, and the counts of max(t/p, p/t) < 1.25, 1.25^2, 1.25^3"""
+    p, t, v = _depth_args(pred, target, valid)
+    sums = torch.empty((p.shape[0], 10), dtype=torch.float64, device=p.device)
+    _lib.call("cr_depth_reduce", p, t, v, sums, p.shape[0], p.shape[1] * p.shape[2])
+    return sums
+
+
+class _SiLog(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, valid, lambd):
+        p, t, v = _depth_args(pred, target, valid)
+        s = depth_reduce(p, t, v).sum(0)
+        n, s1, s2 = s[0], s[1], s[2]
+        loss = torch.sqrt(s2 / n - lambd * (s1 / n) ** 2)
+        ctx.save_for_backward(p, t, v, torch.stack((1.0 / (n * loss), lambd * s1 / (n * n * loss))))
+        return loss.to(f32)
+
+    @staticmethod
+    def backward(ctx, gout):
+        p, t, v, coef = ctx.saved_tensors
+        dpred = torch.empty_like(p)
+        _lib.call("cr_silog_bwd", p, t, v, (coef * gout.double()).to(f32), dpred, p.numel())
+        return dpred, None, None, None
+
+
+def silog_loss(pred, target, valid, lambd=0.5):
+    """SiLogLoss of the reference (util/loss.py) over the valid pixels of the whole batch: sqrt(mean dl^2 - lambd mean(dl)^2),
+    dl = log target - log pred; differentiable in pred (closed-form gradient, one element-wise kernel; exactly 0 on invalid
+    pixels).  pred / target (B,H,W) f32, valid (B,H,W) bool."""
+    return _SiLog.apply(pred, target, valid, float(lambd))
+
+
+DEPTH_METRICS = ("d1", "d2", "d3", "abs_rel", "sq_rel", "rmse", "rmse_log", "log10", "silog")
+
+
+def depth_metrics(pred, target, valid):
+    """eval_depth of the reference (util/metric.py) over the valid pixels of ONE image: pred / target / valid (H,W) or
+    (1,H,W) -> dict of the nine values (python floats)"""
+    if pred.dim() == 2:
+        pred, target, valid = pred[None], target[None], valid[None]
+    assert pred.shape[0] == 1, "depth_metrics takes one image (the reference validates at batch 1)"
+    s = depth_reduce(pred, target, valid)[0]
+    n = s[0]
+    vals = torch.stack((s[7] / n, s[8] / n, s[9] / n, s[3] / n, s[4] / n, torch.sqrt(s[5] / n), torch.sqrt(s[2] / n), s[6] / n,
+                        torch.sqrt(s[2] / n - 0.5 * (s[1] / n) ** 2))).tolist()
+    return dict(zip(DEPTH_METRICS, vals))

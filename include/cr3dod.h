@@ -229,6 +229,42 @@ int cr_scale_residual(cr_ctx* ctx, const void* x, const void* y, const float* ga
  * (util/blocks.py:139, dpt.py:150). */
 int cr_resize_bilinear_ac(cr_ctx* ctx, const void* x, void* y, int B, int h, int w, int Ho, int Wo, int C);
 
+/* ---- Depth-Anything-V2 training (depth/metric_depth/train.py): the backward passes of the ops above and the depth loss.
+ * Activations and their gradients bf16, accumulation f32, parameter gradients f32; no float atomics anywhere: two runs
+ * give the same bits.  `part` arguments are f32 workspaces of 128 * (number of reduced columns) floats. ------------- */
+/* cr_attention_fwd (same kernel body, bit-identical `out`) that also writes lse (B,H,N) f32 = log sum_k exp(scale q.k). */
+int cr_attention_fwd_lse(cr_ctx* ctx, const void* qkv, void* out, float* lse, int B, int N, int H, int D, float scale);
+/* dqkv (B,N,3,H,D) bf16 from qkv, dout (B,N,H,D) bf16 and lse; delta (B,H,N) f32 is a workspace: rowsum(P o dP), which
+ * equals rowsum(dout o out) but is summed in float32 from the recomputed P (the bf16 rounding of `out` is too coarse where
+ * one key dominates a row).  P is recomputed from lse; one pass owns query blocks (delta, then dQ), one key blocks (dK, dV). */
+int cr_attention_bwd(cr_ctx* ctx, const void* qkv, const void* dout, const float* lse, float* delta, void* dqkv, int B, int N,
+                     int H, int D, float scale);
+/* LayerNorm backward (x bf16, or float32 with x_f32 = 1): dx (M,C) in x's type; dgamma / dbeta (C) f32 (either may be NULL) written, or added to when accumulate != 0,
+ * by a two-stage order-fixed column reduction through part (128 * 2C floats). */
+int cr_layernorm_bwd(cr_ctx* ctx, const void* x, const void* dy, const float* gamma, void* dx, float* dgamma, float* dbeta,
+                     float* part, int64_t M, int C, float eps, int accumulate, int x_f32);
+/* the training route's float32 residual stream: LayerNorm of float32 rows (bf16 out; cr_layernorm_bwd with x_f32 = 1 is
+ * its backward) and out = x + gamma * y with float32 x / out and a bf16 branch y (gamma NULL: 1). */
+int cr_layernorm_f32in(cr_ctx* ctx, const float* x, const float* gamma, const float* beta, void* y, int64_t M, int C, float eps);
+int cr_scale_residual_f32(cr_ctx* ctx, const float* x, const void* y, const float* gamma, float* out, int64_t M, int C);
+/* exact GELU out of place (y bit-equal to cr_gelu_inplace) and its backward from the pre-activation x. */
+int cr_gelu_fwd(cr_ctx* ctx, const void* x, void* y, int64_t n);
+int cr_gelu_bwd(cr_ctx* ctx, const void* x, const void* dy, void* dx, int64_t n);
+/* backward of out = x + gamma * y for upstream g (M,C) bf16: dy = gamma * g (bf16), dgamma (=|+=) sum_rows g * y through
+ * part (128 * C floats); dx = g needs no kernel. */
+int cr_layerscale_bwd(cr_ctx* ctx, const void* g, const void* y, const float* gamma, void* dy, float* dgamma, float* part,
+                      int64_t M, int C, int accumulate);
+/* backward of cr_resize_bilinear_ac as a gather: dy (B,Ho,Wo,C) -> dx (B,h,w,C), bf16. */
+int cr_resize_bilinear_ac_bwd(cr_ctx* ctx, const void* dy, void* dx, int B, int h, int w, int Ho, int Wo, int C);
+/* per-image masked sums over pred / target (B,HW) f32 and valid (B,HW) bytes -> sums (B,10) f64: count, sum dl, sum dl^2,
+ * sum |d|/t, sum d^2/t, sum d^2, sum |log10 p - log10 t|, count of max(t/p, p/t) < 1.25^k for k = 1..3 (d = p - t,
+ * dl = log p - log t): everything SiLogLoss (util/loss.py) and eval_depth (util/metric.py) need. */
+int cr_depth_reduce(cr_ctx* ctx, const float* pred, const float* target, const unsigned char* valid, double* sums, int B,
+                    int64_t HW);
+/* dpred[i] = (coef[0] * dl_i - coef[1]) / pred_i on valid pixels, 0 elsewhere; coef: 2 device floats (see vit_bwd.hip). */
+int cr_silog_bwd(cr_ctx* ctx, const float* pred, const float* target, const unsigned char* valid, const float* coef,
+                 float* dpred, int64_t n);
+
 /* ---- convolution stack (MFMA, f32 accumulate, NHWC) --------------------- */
 /* Two arithmetic modes, chosen per call by `act_f32` (the trailing argument of every entry point that touches
  * activations):

@@ -10,6 +10,15 @@ V = 1/3 * sum over boundary polygons of (n . p0) * area.  Faces of A are clipped
 B is clipped exclusively against planes of A with the same orientation, so that coplanar faces of equal orientation are
 counted exactly once while coplanar faces of opposite orientation (touching boxes) both stay and cancel.
 
+Faces of equal orientation that cross or nearly coincide (dot > PAIR_DOT, and the plane of B's face crossing A's face or
+within BAND * scale of it) are split by ONE function instead: with c = nA . nB, g(x) = (nB - c nA) . x - (offB - c offA)
+equals dB(x) on A's plane and -c dA(x) on B's, so "A's face where g <= 0" and "B's face where g > 0" are the two sides of one
+plane through the line in which the faces cross, and tile the common footprint whatever the corners' noise does to that
+line.  A pair of clips by the two planes decides from two quantities (dB on A's corners, dA on B's) that agree only to the
+noise of the corners and the tolerance; for a relative tilt t their lines lie (noise + tol) / sin t apart and the strip
+between them is counted twice or not at all, at the full weight (n . p0) / 3 of a face: IoU 0.78 for a box at 60 m against
+its own float32 round trip, 2.3e-4 too much for equal concentric boxes 5 degrees apart (tests/iou3d_families.py).
+
 Pinned by the reference's own known-answer test ProposalNetwork/utils/tests/test_iou.py:4-27 (IoU = 0.9944) in
 tests/test_iou3d.py, plus analytic cases (axis-aligned overlaps, containment, disjoint, identical, rotated)."""
 import numpy as np
@@ -34,20 +43,23 @@ def box_volume(c):
     return abs(np.linalg.det(np.stack([c[1] - c[0], c[3] - c[0], c[4] - c[0]])))
 
 
-def _clip(poly, n, off, shift):
-    """keep the part of the polygon with n.x - off <= shift."""
+BAND = 1e-3          # times the scale: how close a parallel plane has to come to a face for the pair to be split by g
+PAIR_DOT = 0.9       # ... and how parallel (26 degrees; above 0.71, so a face has at most one partner)
+
+
+def _clip(poly, n, off, shift, strict=False):
+    """keep the part of the polygon with n.x - off <= shift (strict: < shift)."""
     out = []
     m = len(poly)
     if m == 0:
         return out
     d = [float(np.dot(n, p) - off - shift) for p in poly]
+    inside = [(v < 0) if strict else (v <= 0) for v in d]
     for i in range(m):
         j = (i + 1) % m
-        if d[i] <= 0:
+        if inside[i]:
             out.append(poly[i])
-            if d[j] > 0:
-                out.append(poly[i] + (poly[j] - poly[i]) * (d[i] / (d[i] - d[j])))
-        elif d[j] <= 0:
+        if inside[i] != inside[j]:
             out.append(poly[i] + (poly[j] - poly[i]) * (d[i] / (d[i] - d[j])))
     return out
 
@@ -68,23 +80,42 @@ def intersection_volume(c1, c2, tol=None):
     c2 = np.asarray(c2, np.float64)
     o = c1.mean(0)                                     # work relative to box 1's centre
     c1, c2 = c1 - o, c2 - o
+    scale = max(np.abs(c1).max(), np.abs(c2).max(), 1e-30)
     if tol is None:
-        # corners usually come from float32 arithmetic (not exactly planar quads): the coplanarity tolerance has to
-        # cover that noise, or nearly identical boxes lose faces; the volume error it introduces is O(tol * area)
-        tol = 2e-6 * max(np.abs(c1).max(), np.abs(c2).max(), 1e-30)
+        # corners usually come from float32 arithmetic (not exactly planar quads): the tolerance keeps an edge that lies in
+        # a transversal plane of the other box up to that noise; the volume error it introduces is O(tol * area)
+        tol = 2e-6 * scale
+    band = BAND * scale
     n1, o1 = box_planes(c1)
     n2, o2 = box_planes(c2)
+    pair1, pair2 = [-1] * 6, [-1] * 6                   # face of box 1 -> the face of box 2 it is split with by g, and back
+    gn, go = np.zeros((6, 3)), np.zeros(6)
+    for f in range(6):
+        for k in range(6):
+            c = float(np.dot(n1[f], n2[k]))
+            if c > PAIR_DOT:
+                d = [float(np.dot(n2[k], c1[i]) - o2[k]) for i in FACES[f]]
+                if min(d) <= band and max(d) >= -band:
+                    pair1[f], pair2[k] = k, f
+                    gn[f], go[f] = n2[k] - c * n1[f], o2[k] - c * o1[f]
+                    # two faces in one plane (|g| <= tol on all eight corners): g is rounding noise there; g = 0 keeps
+                    # A's face whole and drops B's, as exact g = 0 does
+                    if max(abs(float(np.dot(gn[f], x) - go[f])) for x in [c1[i] for i in FACES[f]] + [c2[i] for i in FACES[k]]) <= tol:
+                        gn[f], go[f] = 0.0, 0.0
     vol = 0.0
     for f in range(6):                                  # faces of box 1 inside box 2 (inclusive)
         poly = [c1[i] for i in FACES[f]]
         for k in range(6):
-            poly = _clip(poly, n2[k], o2[k], +tol)
+            poly = _clip(poly, gn[f], go[f], 0.0) if pair1[f] == k else _clip(poly, n2[k], o2[k], +tol)
         vol += _face_term(poly, n1[f])
     for f in range(6):                                  # faces of box 2 inside box 1; a face coplanar with a face of box 1
         poly = [c2[i] for i in FACES[f]]                # of the SAME orientation was already counted there -> exclusive;
         for k in range(6):                              # opposite orientation (touching boxes) must stay: the two cancel
-            same = float(np.dot(n2[f], n1[k])) > 0.999
-            poly = _clip(poly, n1[k], o1[k], -tol if same else +tol)
+            if pair2[f] == k:
+                poly = _clip(poly, -gn[k], -go[k], 0.0, strict=True)
+            else:
+                same = float(np.dot(n2[f], n1[k])) > 0.999
+                poly = _clip(poly, n1[k], o1[k], -tol if same else +tol)
         vol += _face_term(poly, n2[f])
     return max(vol / 3.0, 0.0)
 

@@ -15,6 +15,19 @@ def cuboid(rng, centre=(0.0, 0.0, 8.0), spread=1.0):
     return box(np.asarray(centre) + rng.normal(size=3) * spread, rng.uniform(0.6, 2.5, 3), rot(rng.normal(size=3), rng.uniform(0, 3)))
 
 
+def grouped_iou3d(d, g):
+    """the grouped kernel (cr_eval_iou_groups) called on one group of cuda:0: the iou3d_fn hook of the host route"""
+    import torch
+    dev = torch.device("cuda:0")
+    d = torch.as_tensor(np.asarray(d), dtype=torch.float32, device=dev).reshape(-1, 8, 3)
+    g = torch.as_tensor(np.asarray(g), dtype=torch.float32, device=dev).reshape(-1, 8, 3)
+    D, G = d.shape[0], g.shape[0]
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
+    iou, _, flag = evalops.eval_iou_groups(True, i32([0, D]), i32([0, G]), torch.tensor([0, D * G], device=dev), D * G, None,
+                                           None, d, g, 0.3, False)
+    return iou.cpu().numpy().reshape(D, G)
+
+
 def gt_rec(img, cat, idx, corners, bbox, depth, area, ignore=0):
     return {"image_id": img, "category_id": cat, "id": idx, "bbox": [float(v) for v in bbox], "area": float(area),
             "bbox3D": np.asarray(corners).tolist(), "depth": float(depth), "ignore2D": int(ignore), "ignore3D": int(ignore)}

@@ -36,15 +36,7 @@ def device_route(ev):
     return packed, out
 
 
-def grouped_iou3d(d, g):
-    """the grouped kernel called on one group: the iou3d_fn hook of the host route"""
-    d = torch.as_tensor(np.asarray(d), dtype=torch.float32, device=DEV).reshape(-1, 8, 3)
-    g = torch.as_tensor(np.asarray(g), dtype=torch.float32, device=DEV).reshape(-1, 8, 3)
-    D, G = d.shape[0], g.shape[0]
-    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=DEV)
-    iou, _, flag = evalops.eval_iou_groups(True, i32([0, D]), i32([0, G]), torch.tensor([0, D * G], device=DEV), D * G, None,
-                                           None, d, g, 0.3, False)
-    return iou.cpu().numpy().reshape(D, G)
+grouped_iou3d = H.grouped_iou3d
 
 
 def group_records(rng, img, cat, G, D, gts, dts, extra_raw=0):

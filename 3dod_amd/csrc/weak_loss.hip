@@ -478,7 +478,8 @@ __global__ __launch_bounds__(WR_T) void k_weak_reduce(WeakRed p, float* __restri
         stats[3] = s_acc[21][0] * inv;                  // z_close
         stats[4] = s_acc[22][0] * inv;                  // 2D IoU
         stats[5] = s_acc[23][0] * inv;                  // conf
-        stats[6] = s_acc[25][0] > 0.f ? s_acc[24][0] / s_acc[25][0] : 0.f;     // total_3D_loss / loss_w_3d
+        // total_3D_loss / loss_w_3d, safely reduced like the terms: no finite entry among valid slots -> NaN
+        stats[6] = s_acc[25][0] > 0.f ? s_acc[24][0] / s_acc[25][0] : (nv > 0.f ? __uint_as_float(0x7fc00000u) : 0.f);
         stats[7] = nv;
     }
 }

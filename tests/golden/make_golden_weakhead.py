@@ -221,8 +221,11 @@ if __name__ == "__main__":
     a = run(21, ['dims', 'pose_alignment', 'pose_ground', 'iou', 'z', 'z_pseudo_gt_patch'])
     b = run(22, ['dims', 'pose_ground2', 'iou', 'z_pseudo_gt_center'])
     c = run(23, ['segmentation', 'depth', 'iou', 'dims'], with_masks=True)
+    # the fused kernels' other depth target (b has pose_ground2, which they do not cover)
+    d = run(24, ['dims', 'pose_alignment', 'pose_ground', 'iou', 'z', 'z_pseudo_gt_center'])
     np.savez_compressed(os.path.join(HERE, "weakhead_a.npz"), **a)
     np.savez_compressed(os.path.join(HERE, "weakhead_b.npz"), **b)
     np.savez_compressed(os.path.join(HERE, "weakhead_c.npz"), **c)
-    for name, r in (("a", a), ("b", b), ("c", c)):
+    np.savez_compressed(os.path.join(HERE, "weakhead_d.npz"), **d)
+    for name, r in (("a", a), ("b", b), ("c", c), ("d", d)):
         print(name, {k: np.asarray(v).reshape(-1).tolist() for k, v in r.items() if k.startswith("loss_")})

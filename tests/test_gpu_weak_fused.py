@@ -206,3 +206,20 @@ def test_fused_path_is_the_one_the_weak_model_trains_with():
         a, b = float(fused[k]), float(comp[k])
         tol = 5e-2 if k == "Cube/loss_normal_vec" else 1e-3
         assert abs(a - b) <= tol * max(1.0, abs(b)), (k, a, b)
+
+
+@pytest.mark.parametrize("name", ["weakhead_a.npz", "weakhead_d.npz"])
+def test_fused_kernels_match_the_reference_recordings(name):
+    """one hop from the reference: its recorded inputs in the slot layout (B = 3, kf = 10 with empty padding slots, raw assembled
+    from the recorded head outputs), ground normals from the RANSAC kernel on the recorded triples, through
+    weak_cube_losses_fused; losses and the gradients of the five head outputs against the REFERENCE's recorded values at the
+    fixtures' 2e-4"""
+    from test_gpu_weak_loss_f64 import run_gpu
+    from test_weak_loss_ref import check_against_recording, fixture_case
+
+    def normals(ground_maps, depth_maps, kbox, triples):
+        return W.ground_normals(ground_maps.to(DEV), d2.ImageList(depth_maps.tensor.to(DEV), depth_maps.image_sizes),
+                                [k.to(DEV) for k in kbox], id_samples=[t.to(DEV) for t in triples])
+    c, rec, slot_of = fixture_case(name, ground_normals=normals)
+    got = run_gpu(c)
+    check_against_recording(got["red"], got["grad"], c, rec, slot_of, show=name)

@@ -107,7 +107,7 @@ def test_polygon_focal_forward_and_gradient():
     assert float(g_ref.abs().max()) > 0
 
 
-@pytest.mark.parametrize("name", ["weakhead_a.npz", "weakhead_b.npz", "weakhead_c.npz"])
+@pytest.mark.parametrize("name", ["weakhead_a.npz", "weakhead_b.npz", "weakhead_c.npz", "weakhead_d.npz"])
 def test_forward_cube_matches_reference_hip(name):
     check_case(name, torch.device("cuda:0"), (None, None))
 

@@ -146,7 +146,7 @@ def check_case(name, dev, hooks, tol=2e-4):
         assert np.allclose(got, rec["out_" + f], rtol=1e-4, atol=1e-4), f
 
 
-@pytest.mark.parametrize("name", ["weakhead_a.npz", "weakhead_b.npz", "weakhead_c.npz"])
+@pytest.mark.parametrize("name", ["weakhead_a.npz", "weakhead_b.npz", "weakhead_c.npz", "weakhead_d.npz"])
 def test_forward_cube_matches_reference_cpu(name):
     from oracle import weak as ow
     check_case(name, torch.device("cpu"), (ow.box_median, ow.Plane, ow.hull8, ow.polygon_focal))

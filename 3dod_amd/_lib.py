@@ -89,7 +89,7 @@ SIGNATURES = {
     "cr_wino_filter": [P, P, P, c_int, c_int, c_int],
     "cr_gemm_batched_f32": [P, P, P, P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64],
     "cr_wino_input": [P, c_int, P, P, P, P, c_int, P, c_int64],
-    "cr_wino_output": [P, c_int, P, P, P, P, P, c_int, c_int64, P, c_int, P],
+    "cr_wino_gemm_output": [P, c_int, P, P, P, P, P, P, c_int, c_int, c_int64, P, c_int, P],
     "cr_wino_dy": [P, c_int, P, P, P, P, c_int, P, c_int64, P],
     "cr_wino_filter_grad": [P, P, P, c_int, c_int, P, P],
     "cr_wgrad_batched_f32": [P, P, P, P, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64],

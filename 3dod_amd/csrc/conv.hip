@@ -28,6 +28,7 @@
 #include "cr_common.h"
 #include "cr_elem.h"
 #include "bn_finalize.h"
+#include "wino_geo.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -1684,6 +1685,201 @@ extern "C" int cr_gemm_batched_f32(cr_ctx* ctx, const float* x, const float* w, 
     const int count = (int)(cr_cdiv(R, 128) * (O / 128));
     hipLaunchKernelGGL(k_gemm_batched_f32, dim3((unsigned)count, (unsigned)batches), dim3(CONV_T), 0, ctx->stream, p,
                        (long long)stride_x, (long long)stride_w, (long long)stride_y, count);
+    CR_LAUNCH_CHECK();
+    return CR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// k_wino_gemm_output: the 16 products of a Winograd F(2x2,3x3) convolution AND its output transform in one kernel.  A block
+// owns 64 rows of V (2 x 2 output tiles) x 64 output channels for ALL 16 transformed positions: the stage loop of
+// conv_igemm_dma_body (same LDS image, same DMA / wait / barrier pattern, mfma_substep<float>) runs 16 x cin / 32 stages back
+// to back -- the prefetch crosses the position boundary, so a block fills and drains its pipeline once -- and the 16 M values
+// of an output element never leave the lane that accumulates them (the MFMA D layout puts position k of (tile, channel) into
+// the same register for every k).
+//   * per-element arithmetic = k_gemm_batched_f32 into M, then y = A^T M A read back from it, bit for bit (the test's
+//     reference: tests/test_gpu_winograd_fused.py): one position's sum starts at 0 and
+//     adds k ascending by stage / sub-step / e; the positions are visited column-major (j outer, i inner, k = 4 i + j) so that
+//     s0 = (q0j + q1j) + q2j, s1 = (q1j - q2j) - q3j build up while column j runs and y[i][0] = (s_i0 + s_i1) + s_i2,
+//     y[i][1] = (s_i1 - s_i2) - s_i3 while j advances; then + bias, ReLU, + acc.
+//   * registers: 1 (acc) + 2 (s) + 4 (y) accumulator sets of 16 floats per lane = 112; the kernel is held to 3 waves per SIMD
+//     (163 VGPRs, no scratch; 32 KiB of LDS per block).  The tile is the measured choice: the MFMA chain of one wave leaves the
+//     LDS / barrier latencies of every stage exposed, and what covers them is other blocks' waves on the same SIMD -- 128 x 64
+//     tiles (307 registers, 1 wave per SIMD) ran the RPN launch in 518 us, 64 x 64 at 2 waves in 489, at 3 waves in 448
+//     (DESIGN.md section 2 item 12).
+//   * a row tile may cover several maps (the small pyramid levels): every output row finds its map from tbase (a select chain
+//     over the at most 8 maps: no dynamic indexing of the kernel argument).
+//   * rows >= T read zeros (each plane has its own buffer descriptor of T * cin floats) and store nothing.
+// ---------------------------------------------------------------------------
+#define WINO_BM 64
+#define WINO_BN 64
+__global__ __launch_bounds__(CONV_T) __attribute__((amdgpu_waves_per_eu(3, 3)))
+void k_wino_gemm_output(WinoGeo g, const float* __restrict__ V, const float* __restrict__ U, const float* __restrict__ bias,
+                        int relu, int cin) {
+    constexpr int BM = WINO_BM, BN = WINO_BN, SUB = 16, KU = 2, BK = KU * SUB;   // KU 16-wide k sub-steps per stage
+    constexpr int TP = BM / 4 / 16, TC = BN / 16;                          // 4 x 1 waves: 16 rows x all 64 channels each
+    constexpr int XS = BM * 32, WS = BN * 32, STAGE = KU * (XS + WS);     // u16 units; X(u = 0, 1), W(u = 0, 1)
+    static_assert(TP == 1 && TC == 4 && BM == 64 && BN == 64, "one row / one weight row per thread; the waits name the fragments");
+    __shared__ __attribute__((aligned(1024))) u16 smem[2 * STAGE];         // 32 KiB
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cout = g.C, T = g.T;
+    const int n_tiles = cout / BN;
+    const int bid = xcd_swizzle((int)blockIdx.x, (int)gridDim.x);
+    const int nt = bid % n_tiles, mt = bid / n_tiles;
+    const int m0 = mt * BM, n0 = nt * BN;
+
+    // this lane fetches row tid >> 2 of the V tile and of the U tile; chunk swizzled on the source side (lds_off's image)
+    const unsigned csrc = (unsigned)(((tid & 3) ^ ((-(tid >> 4)) & 3)) * 16);
+    const unsigned xoff = (unsigned)((m0 + (tid >> 2)) * cin) * 4u + csrc;
+    const unsigned woff = (unsigned)((n0 + (tid >> 2)) * cin) * 4u + csrc;
+    const size_t planeV = (size_t)T * cin, planeU = (size_t)cout * cin;
+    const unsigned v_bytes = (unsigned)(planeV * 4), u_bytes = (unsigned)(planeU * 4);
+    const int nst = cin / BK, total = 16 * nst;
+
+    int nv = 0, ns = 0;                                                    // visit (0..15) and stage within it of the next fetch
+    auto issue = [&](int buf) {
+        const int k = 4 * (nv & 3) + (nv >> 2);                            // column-major visit -> plane
+        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(V + (size_t)k * planeV), 0, v_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)(U + (size_t)k * planeU), 0, u_bytes, 0x00020000);
+        const unsigned kb = (unsigned)(ns * BK) * 4u;
+        u16* base = smem + buf * STAGE;
+#pragma unroll
+        for (int u = 0; u < KU; ++u) dma16(rx, base + u * XS + (wave * 16) * 32, xoff + kb + (unsigned)(u * SUB) * 4u);
+#pragma unroll
+        for (int u = 0; u < KU; ++u) dma16(rw, base + KU * XS + u * WS + (wave * 16) * 32, woff + kb + (unsigned)(u * SUB) * 4u);
+        if (++ns == nst) { ns = 0; ++nv; }
+    };
+
+    const int poff = wave * (BM / 4);
+    const int fr = lane & 15, fc = lane >> 4;
+    const unsigned lds0 = lds_addr(smem);
+    unsigned xa[TP], wa[TC];
+#pragma unroll
+    for (int j = 0; j < TP; ++j) xa[j] = (unsigned)lds_off(poff + j * 16 + fr, fc) * 2u;
+#pragma unroll
+    for (int i = 0; i < TC; ++i) wa[i] = (unsigned)lds_off(i * 16 + fr, fc) * 2u;
+
+    f32x4 acc[TC][TP], s0[TC][TP], s1[TC][TP], y[2][2][TC][TP];
+    const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < TC; ++i)
+#pragma unroll
+        for (int j = 0; j < TP; ++j) { s0[i][j] = s1[i][j] = y[0][0][i][j] = y[0][1][i][j] = y[1][0][i][j] = y[1][1][i][j] = zero; }
+
+    issue(0);
+    int gs = 0;                                                            // stages done
+    for (int jc = 0; jc < 4; ++jc) {
+#pragma unroll
+        for (int ir = 0; ir < 4; ++ir) {
+#pragma unroll
+            for (int i = 0; i < TC; ++i)
+#pragma unroll
+                for (int j = 0; j < TP; ++j) acc[i][j] = zero;
+            for (int st = 0; st < nst; ++st, ++gs) {
+                const int buf = gs & 1;
+                if (gs + 1 < total) {
+                    issue(buf ^ 1);
+                    static_assert(2 * KU == 4, "vmcnt literal");
+                    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");         // this stage has landed (this wave's 4 DMAs)
+                } else {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                }
+                __builtin_amdgcn_s_barrier();                                // ... and every other wave's
+                const unsigned sb = lds0 + (unsigned)(buf * STAGE) * 2u;
+#pragma unroll
+                for (int u = 0; u < KU; ++u) {
+                    u32x4 xf[TP], wf[TC];
+#pragma unroll
+                    for (int j = 0; j < TP; ++j) xf[j] = lds_read16_asm(sb + (unsigned)(u * XS) * 2u + xa[j]);
+#pragma unroll
+                    for (int i = 0; i < TC; ++i) wf[i] = lds_read16_asm(sb + (unsigned)(KU * XS + u * WS) * 2u + wa[i]);
+                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xf[0]), "+v"(wf[0]), "+v"(wf[1]), "+v"(wf[2]), "+v"(wf[3]));
+                    mfma_substep<float, TC, TP>(wf, xf, acc);
+                }
+                asm volatile("" ::: "memory");
+                __builtin_amdgcn_s_barrier();                                // everyone is done with `buf` before it is refilled
+            }
+            // acc = q[ir][jc], a rounded float32 of its own: fold the column
+#pragma unroll
+            for (int i = 0; i < TC; ++i)
+#pragma unroll
+                for (int j = 0; j < TP; ++j) {
+                    if (ir == 0) s0[i][j] = acc[i][j];
+                    else if (ir == 1) { s0[i][j] = s0[i][j] + acc[i][j]; s1[i][j] = acc[i][j]; }
+                    else if (ir == 2) { s0[i][j] = s0[i][j] + acc[i][j]; s1[i][j] = s1[i][j] - acc[i][j]; }
+                    else s1[i][j] = s1[i][j] - acc[i][j];
+                }
+        }
+        // column jc of s is complete: fold the rows (jc is block-uniform)
+#pragma unroll
+        for (int i = 0; i < TC; ++i)
+#pragma unroll
+            for (int j = 0; j < TP; ++j) {
+                if (jc == 0) { y[0][0][i][j] = s0[i][j]; y[1][0][i][j] = s1[i][j]; }
+                else if (jc == 1) {
+                    y[0][0][i][j] = y[0][0][i][j] + s0[i][j]; y[1][0][i][j] = y[1][0][i][j] + s1[i][j];
+                    y[0][1][i][j] = s0[i][j]; y[1][1][i][j] = s1[i][j];
+                } else if (jc == 2) {
+                    y[0][0][i][j] = y[0][0][i][j] + s0[i][j]; y[1][0][i][j] = y[1][0][i][j] + s1[i][j];
+                    y[0][1][i][j] = y[0][1][i][j] - s0[i][j]; y[1][1][i][j] = y[1][1][i][j] - s1[i][j];
+                } else { y[0][1][i][j] = y[0][1][i][j] - s0[i][j]; y[1][1][i][j] = y[1][1][i][j] - s1[i][j]; }
+            }
+    }
+
+    // + bias, ReLU, + acc, store: a lane holds 4 consecutive channels of the 2 x 2 pixels of TP tiles
+    const int cg = lane >> 4, pl = lane & 15;
+#pragma unroll
+    for (int j = 0; j < TP; ++j) {
+        const int m = m0 + poff + j * 16 + pl;
+        if (m >= T) continue;
+        int H = g.m[0].H, W = g.m[0].W, tb = 0;
+        float* dst = g.m[0].dst;
+        const float* add = g.m[0].acc;
+#pragma unroll
+        for (int q = 1; q < WINO_MAX_MAPS; ++q)
+            if (q < g.n && m >= g.m[q].tbase) { H = g.m[q].H; W = g.m[q].W; tb = g.m[q].tbase; dst = g.m[q].dst; add = g.m[q].acc; }
+        const int th = H >> 1, tw = W >> 1;
+        const int t = m - tb;
+        const int n = t / (th * tw), r = t - n * (th * tw);
+        const int ty = r / tw, tx = r - ty * tw;
+#pragma unroll
+        for (int i = 0; i < TC; ++i) {
+            const int ch = n0 + i * 16 + 4 * cg;
+            f32x4 b = zero;                                                  // (a parameter may sit at any 4-byte offset of a flat buffer)
+            if (bias) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) b[e] = bias[ch + e];
+            }
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                const size_t p = (((size_t)n * H + 2 * ty + a) * W + 2 * tx) * cout + ch;
+                f32x4 y0 = y[a][0][i][j] + b, y1 = y[a][1][i][j] + b;
+                if (relu) { y0 = __builtin_elementwise_max(y0, zero); y1 = __builtin_elementwise_max(y1, zero); }
+                if (add) { y0 += *(const f32x4*)(add + p); y1 += *(const f32x4*)(add + p + cout); }
+                *(f32x4*)(dst + p) = y0;
+                *(f32x4*)(dst + p + cout) = y1;
+            }
+        }
+    }
+}
+
+// ys[i] (N_i,H_i,W_i,cout) = A^T [sum over cin of V[k] (T,cin) @ U[k] (cout,cin)^T] A + bias, ReLU if asked, + accs[i] (may be
+// NULL / hold NULLs): what cr_gemm_batched_f32 into M (16,T,cout) followed by an output transform gives, without M
+extern "C" int cr_wino_gemm_output(cr_ctx* ctx, int n, const float* V, const float* U, float* const* ys, const int* Ns,
+                                   const int* Hs, const int* Ws, int cin, int cout, int64_t T, const float* bias, int relu,
+                                   const float* const* accs) {
+    CR_CHECK_ARG(ctx && V && U && ys && Ns && Hs && Ws, "cr_wino_gemm_output: NULL pointer");
+    CR_CHECK_ARG(cin > 0 && cin % 32 == 0 && cout > 0 && cout % WINO_BN == 0, "cr_wino_gemm_output: cin %% 32 == 0, cout %% %d == 0", WINO_BN);
+    // 32-bit byte offsets inside one plane (rows up to T + 63 are addressed and read as zeros)
+    CR_CHECK_ARG(T > 0 && (T + WINO_BM) * cin * 4 < (1ll << 31) && (int64_t)cout * cin * 4 < (1ll << 31),
+                 "cr_wino_gemm_output: a plane of V or U exceeds 2 GiB");
+    WinoGeo g;
+    unsigned blocks = 0;
+    int vec = 1;
+    int rc = wino_geo("cr_wino_gemm_output", g, n, nullptr, ys, accs, Ns, Hs, Ws, cout, T, WINO_BM, &blocks, &vec);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i) CR_CHECK_ARG(ys[i], "cr_wino_gemm_output: NULL map %d", i);
+    const unsigned grid = (unsigned)(cr_cdiv(T, WINO_BM) * (cout / WINO_BN));
+    hipLaunchKernelGGL(k_wino_gemm_output, dim3(grid), dim3(CONV_T), 0, ctx->stream, g, V, U, bias, relu, cin);
     CR_LAUNCH_CHECK();
     return CR_OK;
 }

@@ -1,34 +1,26 @@
 // Winograd F(2x2, 3x3) transforms for the stride-1, pad-1, 3x3 convolutions of the pyramid heads (float32, NHWC):
 //   Y = A^T [ sum_c (G g G^T) .* (B^T d B) ] A        2.25x fewer multiplies than the direct form
-// The 16 element-wise products over channels are 16 GEMMs (tiles x C) @ (C x O), run by the existing 1x1 grouped
-// convolution launches (cr_conv2d_fwd_group); this file holds the three transforms around them:
+// The 16 element-wise products over channels are 16 GEMMs (tiles x C) @ (C x O); one kernel runs them and folds the output
+// transform y = A^T M A into its registers (conv.hip: k_wino_gemm_output).  This file holds the transforms around it:
 //   cr_wino_filter   U[16][O][C] = G g G^T of every (output, input) channel pair -- forward (g = w[o][.][.][c]) or
 //                    backward-data (U[16][C][O] from the flipped taps: dX = conv(dY, rot180(w)^T))
 //   cr_wino_input    V[16][T][C] = B^T d B of every 4 x 4 input window (2 x 2 output tile), zero padding at the borders;
 //                    T = tiles of all maps of the call (pyramid levels x images), one row block per map
-//   cr_wino_output   y = A^T M A (+ bias, ReLU, + accumulate) from M[16][T][O], written to each map's own tensor
+//   cr_wino_dy       dM[16][T][O] = A dY A^T, the adjoint of the output transform, and cr_wino_filter_grad, G^T dU G: the
+//                    weight gradient's way there and back
 // float32 error of F(2x2, 3x3) against float64: 6e-7 of the output range (direct: 2e-7; scripts/winograd_numerics.py).
 // Reference call sites: the 3x3 convolutions of detectron2's FPN output / RPN head as used by cubercnn/modeling (the
 // arithmetic they replace is torch.nn.functional.conv2d).
 #include "cr_common.h"
+#include "wino_geo.h"
 
-#define WINO_MAX_MAPS 8
-struct WinoMap { const float* src; float* dst; const float* acc; int N, H, W, tbase, blk0; };
-struct WinoGeo { WinoMap m[WINO_MAX_MAPS]; int n, C, T; };
-
-__device__ __forceinline__ int wino_find(const WinoGeo& g, int blk) {
-    int i = 0;
-    while (i + 1 < g.n && blk >= g.m[i + 1].blk0) ++i;
-    return i;
-}
-
-// The three map-side transforms share one decomposition: a wave owns one 2 x 2 output tile at a time and its 64 lanes cover
+// The map-side transforms share one decomposition: a wave owns one 2 x 2 output tile at a time and its 64 lanes cover
 // 64 * VEC consecutive channels with VEC floats each (16-byte accesses for C % 256 == 0: whole 1 KB channel rows per wave
 // instruction); a block of 4 waves takes TPB consecutive tiles of one map and one channel group.
 typedef float vf1 __attribute__((ext_vector_type(1)));
 typedef float vf2 __attribute__((ext_vector_type(2)));
 typedef float vf4 __attribute__((ext_vector_type(4)));
-#define WINO_TPB 8          // tiles per block of the input / output transforms
+#define WINO_TPB 8          // tiles per block of the input transform
 #define WINO_TPB_DY 16      // ... of the dY transform (fewer bias atomics)
 #define WINO_DB_SLOTS 16    // partial bias-gradient rows the dY transform spreads its atomics over
 
@@ -81,41 +73,6 @@ __global__ __launch_bounds__(256) void k_wino_input(WinoGeo g, float* __restrict
             *(VT*)(o + (i * 4 + 1) * plane) = t[i][1] + t[i][2];
             *(VT*)(o + (i * 4 + 2) * plane) = t[i][2] - t[i][1];
             *(VT*)(o + (i * 4 + 3) * plane) = t[i][1] - t[i][3];
-        }
-    }
-}
-
-template <typename VT>
-__global__ __launch_bounds__(256) void k_wino_output(WinoGeo g, const float* __restrict__ M, const float* __restrict__ bias, int relu) {
-    constexpr int VEC = sizeof(VT) / 4;
-    const WinoMap& m = g.m[wino_find(g, (int)blockIdx.x)];
-    const int C = g.C, th = m.H >> 1, tw = m.W >> 1;     // C: OUTPUT channels of the product here
-    const size_t plane = (size_t)g.T * C;
-    for (int k = threadIdx.x >> 6; k < WINO_TPB; k += 4) {
-        const WinoTile w = wino_tile<VEC>(g, m, k, WINO_TPB);
-        if (!w.ok) break;
-        VT b = (VT)(0.f);                               // (a parameter may sit at any 4-byte offset of a flat buffer)
-        if (bias) {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) b[e] = bias[w.c + e];
-        }
-        const float* o = M + ((size_t)m.tbase + ((size_t)w.n * th + w.ty) * tw + w.tx) * C + w.c;
-        VT q[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) q[i][j] = *(const VT*)(o + (i * 4 + j) * plane);
-        VT s[2][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { s[0][j] = (q[0][j] + q[1][j]) + q[2][j]; s[1][j] = (q[1][j] - q[2][j]) - q[3][j]; }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            VT y0 = (s[i][0] + s[i][1]) + s[i][2] + b, y1 = (s[i][1] - s[i][2]) - s[i][3] + b;
-            const size_t p = (((size_t)w.n * m.H + 2 * w.ty + i) * m.W + 2 * w.tx) * C + w.c;
-            if (relu) { y0 = __builtin_elementwise_max(y0, (VT)(0.f)); y1 = __builtin_elementwise_max(y1, (VT)(0.f)); }
-            if (m.acc) { y0 += *(const VT*)(m.acc + p); y1 += *(const VT*)(m.acc + p + C); }
-            *(VT*)(m.dst + p) = y0;
-            *(VT*)(m.dst + p + C) = y1;
         }
     }
 }
@@ -225,27 +182,6 @@ __global__ __launch_bounds__(256) void k_wino_filter_grad(const float* __restric
     }
 }
 
-static int wino_geo(const char* who, WinoGeo& g, int n, const float* const* srcs, float* const* dsts, const float* const* accs,
-                    const int* Ns, const int* Hs, const int* Ws, int C, int64_t T, int tpb, unsigned* blocks, int* vec) {
-    CR_CHECK_ARG(n >= 1 && n <= WINO_MAX_MAPS, "%s: 1..%d maps", who, WINO_MAX_MAPS);
-    CR_CHECK_ARG(C > 0 && C % 64 == 0, "%s: channels %% 64", who);
-    g.n = n; g.C = C; g.T = (int)T;
-    const int v = C % 256 == 0 ? 4 : C % 128 == 0 ? 2 : 1;           // floats per lane: 16-byte accesses when the channels allow
-    *vec = v;
-    int tb = 0, blk = 0;
-    for (int i = 0; i < n; ++i) {
-        CR_CHECK_ARG(Ns[i] > 0 && Hs[i] > 0 && Ws[i] > 0 && Hs[i] % 2 == 0 && Ws[i] % 2 == 0, "%s: map %d needs even H and W", who, i);
-        g.m[i].src = srcs ? srcs[i] : nullptr; g.m[i].dst = dsts ? dsts[i] : nullptr; g.m[i].acc = accs ? accs[i] : nullptr;
-        g.m[i].N = Ns[i]; g.m[i].H = Hs[i]; g.m[i].W = Ws[i]; g.m[i].tbase = tb; g.m[i].blk0 = blk;
-        tb += Ns[i] * (Hs[i] / 2) * (Ws[i] / 2);
-        blk += (int)cr_cdiv((int64_t)Ns[i] * (Hs[i] / 2) * (Ws[i] / 2), tpb) * (C / (64 * v));
-    }
-    CR_CHECK_ARG(tb == T && (int64_t)T * C * 16 < (1ll << 40), "%s: T = %lld does not match the maps (%d tiles)", who, (long long)T, tb);
-    for (int i = n; i < WINO_MAX_MAPS; ++i) g.m[i] = g.m[n - 1];
-    *blocks = (unsigned)blk;
-    return CR_OK;
-}
-
 extern "C" int cr_wino_filter(cr_ctx* ctx, const float* w_krsc, float* U, int O, int C, int backward) {
     CR_CHECK_ARG(ctx && w_krsc && U && O > 0 && C > 0, "cr_wino_filter: bad args");
     hipLaunchKernelGGL(k_wino_filter, dim3((unsigned)cr_cdiv((int64_t)O * C, 256)), dim3(256), 0, ctx->stream, w_krsc, U, O, C, backward ? 1 : 0);
@@ -265,22 +201,6 @@ extern "C" int cr_wino_input(cr_ctx* ctx, int n, const float* const* xs, const i
     if (vec == 4) hipLaunchKernelGGL(k_wino_input<vf4>, dim3(blocks), dim3(256), 0, ctx->stream, g, V);
     else if (vec == 2) hipLaunchKernelGGL(k_wino_input<vf2>, dim3(blocks), dim3(256), 0, ctx->stream, g, V);
     else hipLaunchKernelGGL(k_wino_input<vf1>, dim3(blocks), dim3(256), 0, ctx->stream, g, V);
-    CR_LAUNCH_CHECK();
-    return CR_OK;
-}
-
-// M (16, T, O) -> ys[i] (N_i, H_i, W_i, O) = A^T M A + bias, ReLU if asked, + accs[i] (may be NULL / hold NULLs)
-extern "C" int cr_wino_output(cr_ctx* ctx, int n, const float* M, float* const* ys, const int* Ns, const int* Hs, const int* Ws,
-                              int O, int64_t T, const float* bias, int relu, const float* const* accs) {
-    CR_CHECK_ARG(ctx && M && ys && Ns && Hs && Ws, "cr_wino_output: NULL pointer");
-    WinoGeo g;
-    unsigned blocks = 0;
-    int vec = 1;
-    int rc = wino_geo("cr_wino_output", g, n, nullptr, ys, accs, Ns, Hs, Ws, O, T, WINO_TPB, &blocks, &vec);
-    if (rc) return rc;
-    if (vec == 4) hipLaunchKernelGGL(k_wino_output<vf4>, dim3(blocks), dim3(256), 0, ctx->stream, g, M, bias, relu);
-    else if (vec == 2) hipLaunchKernelGGL(k_wino_output<vf2>, dim3(blocks), dim3(256), 0, ctx->stream, g, M, bias, relu);
-    else hipLaunchKernelGGL(k_wino_output<vf1>, dim3(blocks), dim3(256), 0, ctx->stream, g, M, bias, relu);
     CR_LAUNCH_CHECK();
     return CR_OK;
 }

@@ -1206,10 +1206,12 @@ def conv_bwd_weight_group_raw(gs, xs, dws, dbs, Cin, Cout, k, pad):
 
 # --------------------------------------------------------------------------
 # Winograd F(2x2, 3x3) route of the grouped 3x3 convolutions (float32, stride 1, pad 1, even maps, one shared weight):
-# input transform -> 16 GEMMs (two grouped 1x1 launches of 8) -> output transform.  2.25x fewer multiplies; the V / M planes
-# (16 x tiles x C floats each) are persistent per (tiles, channels) and must exist before a graph capture (first eager pass).
+# input transform -> one kernel for the 16 GEMMs and the output transform (cr_wino_gemm_output).  2.25x fewer multiplies; the V
+# planes (16 x tiles x C floats), and the dM planes of the weight gradient, are persistent per (tiles, channels) and must exist
+# before a graph capture (first eager pass).
 # --------------------------------------------------------------------------
 _WINO_BUF = {}
+_WINO_DM = {}
 
 
 def winograd_on():
@@ -1221,11 +1223,22 @@ def _wino_buffers(T, C, O, dev):
     ent = _WINO_BUF.get(key)
     if ent is None:
         if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            raise _lib.CrError("winograd: the V / M planes must be allocated before the graph capture (run one eager pass first)")
+            raise _lib.CrError("winograd: the V planes must be allocated before the graph capture (run one eager pass first)")
         # U (16, O, C) is the head of a flat buffer whose 16 * O tail holds the partial bias gradients of the weight-gradient
         # route (one zero-fill covers both)
-        ent = _WINO_BUF[key] = (torch.empty((16, T, C), dtype=f32, device=dev), torch.empty((16, T, O), dtype=f32, device=dev),
+        ent = _WINO_BUF[key] = (torch.empty((16, T, C), dtype=f32, device=dev),
                                 torch.empty((16 * O * C + 16 * O,), dtype=f32, device=dev))
+    return ent
+
+
+def _wino_dm_buffer(T, O, dev):
+    """dM (16, T, O) = A dY A^T of the weight-gradient route (the forward and backward-data routes keep M in registers)"""
+    key = (T, O, str(dev))
+    ent = _WINO_DM.get(key)
+    if ent is None:
+        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise _lib.CrError("winograd: the dM planes must be allocated before the graph capture (run one eager pass first)")
+        ent = _WINO_DM[key] = torch.empty((16, T, O), dtype=f32, device=dev)
     return ent
 
 
@@ -1248,12 +1261,6 @@ def _wino_plan(xs, ws, bs, k, pad):
     return [x.shape[0] * (x.shape[1] // 2) * (x.shape[2] // 2) >= WINO_MIN_TILES for x in xs]
 
 
-def wino_gemm_raw(V, U, M, T, cin, cout):
-    """M[k] (T,cout) = V[k] (T,cin) @ U[k] (cout,cin)^T for the 16 transformed positions: one launch (module-level so that
-    bench.py can bracket it with events)"""
-    _lib.call("cr_gemm_batched_f32", V, U, M, T, cin, cout, 16, T * cin, cout * cin, T * cout)
-
-
 def wino_conv3x3_group(srcs, w_krsc, dsts, bias, relu, accs, backward, keep_v=False):
     """dsts[i] = conv3x3(srcs[i], w) (+ bias, ReLU, + accs[i]) for n maps sharing ONE weight: forward (w (O,3,3,C) applied to
     (N,H,W,C) maps) or, backward = True, the backward-data of that convolution (srcs = dY with O channels, dsts = dX with C).
@@ -1265,16 +1272,15 @@ def wino_conv3x3_group(srcs, w_krsc, dsts, bias, relu, accs, backward, keep_v=Fa
     cin, cout = (O, C) if backward else (C, O)          # channels of the maps going in / coming out
     dev = srcs[0].device
     T = sum(x.shape[0] * (x.shape[1] // 2) * (x.shape[2] // 2) for x in srcs)
-    V, M, U = _wino_buffers(T, cin, cout, dev)
+    V, U = _wino_buffers(T, cin, cout, dev)
     U = U[:16 * O * C]
     if keep_v:
         V = torch.empty((16, T, cin), dtype=f32, device=dev)
     _lib.call("cr_wino_filter", w_krsc, U, O, C, int(backward))
     Ns, Hs, Ws = _int_table([x.shape[0] for x in srcs]), _int_table([x.shape[1] for x in srcs]), _int_table([x.shape[2] for x in srcs])
     _lib.call("cr_wino_input", len(srcs), cast(_ptr_table(srcs)), cast(Ns), cast(Hs), cast(Ws), cin, V, T)
-    wino_gemm_raw(V, U, M, T, cin, cout)
-    _lib.call("cr_wino_output", len(dsts), M, cast(_ptr_table(dsts)), cast(Ns), cast(Hs), cast(Ws), cout, T, bias, int(relu),
-              cast(_ptr_table(accs)) if accs is not None else None)
+    _lib.call("cr_wino_gemm_output", len(dsts), V, U, cast(_ptr_table(dsts)), cast(Ns), cast(Hs), cast(Ws), cin, cout, T, bias,
+              int(relu), cast(_ptr_table(accs)) if accs is not None else None)
     return V if keep_v else None
 
 
@@ -1297,7 +1303,8 @@ def wino_wgrad_group(gs, xs, w_sink, b_sink, v_saved=None):
     O, C = gs[0].shape[3], xs[0].shape[3]
     dev = xs[0].device
     T = sum(x.shape[0] * (x.shape[1] // 2) * (x.shape[2] // 2) for x in xs)
-    V, M, U = _wino_buffers(T, C, O, dev)
+    V, U = _wino_buffers(T, C, O, dev)
+    M = _wino_dm_buffer(T, O, dev)
     Ns, Hs, Ws = _int_table([x.shape[0] for x in xs]), _int_table([x.shape[1] for x in xs]), _int_table([x.shape[2] for x in xs])
     if v_saved is not None:                 # the forward pass kept B^T x B of exactly these maps
         assert v_saved.shape == (16, T, C)

@@ -391,22 +391,24 @@ int cr_conv2d_grouped_bwd_data(cr_ctx* ctx, const void* dy, const float* w, void
 int cr_conv2d_grouped_bwd_weight(cr_ctx* ctx, const void* dy, const void* x, float* dw, float* dbias, int N, int H, int W,
                                  int Cin, int Cout, int groups, int ks, int stride, int pad, int accumulate, int act_f32,
                                  float* ws, int64_t ws_floats);
-/* Winograd F(2x2, 3x3) transforms for stride-1, pad-1 3x3 convolutions on float32 NHWC maps (csrc/winograd.hip): the 16
- * products over channels in between are 1x1 grouped convolutions (cr_conv2d_fwd_group) on V / U / M -- the arithmetic replaces
- * torch.nn.functional.conv2d as called by detectron2's RPN head / FPN output convolutions in the reference's model.
+/* Winograd F(2x2, 3x3) route of stride-1, pad-1 3x3 convolutions on float32 NHWC maps (csrc/winograd.hip, csrc/conv.hip): the
+ * filter and input transforms, then ONE kernel for the 16 products over channels and the output transform -- the arithmetic
+ * replaces torch.nn.functional.conv2d as called by detectron2's RPN head / FPN output convolutions in the reference's model.
  *   cr_wino_filter  w (O,3,3,C) KRSC -> U (16,O,C) = G g G^T; backward != 0: U (16,C,O) of the 180-degree-rotated taps
  *                   (backward-data = the same convolution with those filters on dY)
  *   cr_wino_input   xs: n host-array pointers to (N_i,H_i,W_i,C) maps (H_i, W_i even) -> V (16,T,C), T = sum N_i H_i W_i / 4
- *   cr_wino_output  M (16,T,O) -> ys[i] (N_i,H_i,W_i,O) = A^T M A + bias (O, or NULL), ReLU if relu, + accs[i] if given */
+ *   cr_wino_gemm_output  V (16,T,cin), U (16,cout,cin) -> ys[i] (N_i,H_i,W_i,cout) = A^T M A + bias (cout, or NULL), ReLU if
+ *                   relu, + accs[i] if given, with M[k] = V[k] @ U[k]^T kept in registers: bit-identical to cr_gemm_batched_f32
+ *                   into M (16,T,cout) followed by that transform (cin % 32 == 0, cout % 64 == 0, ys 16-byte aligned) */
 int cr_wino_filter(cr_ctx* ctx, const float* w_krsc, float* U, int O, int C, int backward);
-/* the products in between as ONE launch: y[b] (R,O) = x[b] (R,K) @ w[b] (O,K)^T for b < batches, float32, operands of batch b
+/* batched products as ONE launch (the Winograd products written out; benchmarks and tests use it): y[b] (R,O) = x[b] (R,K) @ w[b] (O,K)^T for b < batches, float32, operands of batch b
  * at base + b * stride_* elements (O % 128 == 0, K % 32 == 0) */
 int cr_gemm_batched_f32(cr_ctx* ctx, const float* x, const float* w, float* y, int R, int K, int O, int batches,
                         int64_t stride_x, int64_t stride_w, int64_t stride_y);
 int cr_wino_input(cr_ctx* ctx, int n, const float* const* xs, const int* Ns, const int* Hs, const int* Ws, int C,
                   float* V, int64_t T);
-int cr_wino_output(cr_ctx* ctx, int n, const float* M, float* const* ys, const int* Ns, const int* Hs, const int* Ws,
-                   int O, int64_t T, const float* bias, int relu, const float* const* accs);
+int cr_wino_gemm_output(cr_ctx* ctx, int n, const float* V, const float* U, float* const* ys, const int* Ns, const int* Hs,
+                        const int* Ws, int cin, int cout, int64_t T, const float* bias, int relu, const float* const* accs);
 /* weight gradient the same way: dU[k] (O,C) = dM[k]^T V[k] over the tiles (cr_wgrad_batched_f32: the 16 positions in one launch), with
  *   cr_wino_dy           dys: n maps (N_i,H_i,W_i,O) -> dM (16,T,O) = A dY A^T; db_part (16,O), zeroed by the caller, +=
  *                        partial channel sums of dY when given (atomics spread over 16 rows)
